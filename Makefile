@@ -15,7 +15,7 @@ test-gpu:
 	$(PY) -m pytest tests -q -m gpu
 
 bench:
-	$(PY) bench.py --gpus 1 --steps 20 --warmup 5
+	$(PY) bench.py --gpus 1 --steps 20 --warmup 5 --full
 
 clean:
 	rm -rf kubegpu_amd/csrc/bin kubegpu_amd/_ext kubegpu_amd/_schedcore*.so

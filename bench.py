@@ -19,10 +19,18 @@ Measures the two headline metrics fixed by BASELINE.json:
    (uint8 buffer — the record's dtype/curve_point keys say so).
 2. **p50 pod-schedule latency (ms)** on a synthetic pod-request stream
    (mixed 1/2/4/8-GPU pods against an 8×MI355X topology), reported as
-   extra keys (schedule_p50_ms / schedule_p95_ms).
+   extra keys (schedule_p50_ms / schedule_p95_ms).  This is a CPU-side
+   measurement of its own, so it runs only with --full; a plain run
+   does just what metric 1 needs.
+
+--dump-outputs DIR writes what the last timed step computed (the
+destination buffer of the k=1 copy) to DIR/dst.npy as float32, so two
+builds can be compared output for output.  Inputs are constant, hence
+identical from run to run.
 
 Launch (driver contract):
   python bench.py --gpus 1 --steps K --warmup W            # single GPU
+  python bench.py --gpus 1 --steps K --warmup W --full     # + schedule latency
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N ...        # N ranks
 Rank 0 prints exactly one JSON line.
@@ -153,6 +161,40 @@ def _schedule_and_pin(n_gpus: int, local_rank: int):
         return {"scheduled_devices": None, "sched_error": str(e)[:200]}
 
 
+# --dump-outputs budget: whole buffer up to this many elements, else
+# head + tail + a fixed seeded sample (float32 -> 16 MiB on disk).
+_DUMP_MAX_ELEMS = 4 << 20
+_DUMP_EDGE_ELEMS = 1 << 16
+
+
+def _dump_outputs(out_dir: str, dst) -> None:
+    """Write the timed path's last output as out_dir/dst.npy (float32).
+
+    Buffers above _DUMP_MAX_ELEMS are sampled: both edges (where a copy
+    kernel's tail handling lives) plus sorted positions drawn from a
+    fixed-seed generator, so every run picks the same elements.
+    """
+    import numpy as np
+    import torch
+
+    flat = dst.reshape(-1)
+    n = flat.numel()
+    if n > _DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu").manual_seed(0)
+        mid = torch.randint(
+            0, n, (_DUMP_MAX_ELEMS - 2 * _DUMP_EDGE_ELEMS,), generator=g
+        ).sort().values
+        idx = torch.cat([
+            torch.arange(_DUMP_EDGE_ELEMS),
+            mid,
+            torch.arange(n - _DUMP_EDGE_ELEMS, n),
+        ])
+        flat = flat[idx.to(flat.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "dst.npy"),
+            flat.to(torch.float32).cpu().numpy())
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -164,6 +206,11 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--bytes", type=int, default=1 << 30)
     ap.add_argument("--pods", type=int, default=2000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the pod-schedule latency stream "
+                         "(schedule_p50_ms / schedule_p95_ms keys)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/dst.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -176,6 +223,10 @@ def main() -> int:
             f"{args.gpus} --master-addr 127.0.0.1 bench.py --gpus {args.gpus} ...",
             file=sys.stderr,
         )
+        return 2
+    if args.dump_outputs and world > 1:
+        print("bench.py: --dump-outputs covers the single-process run only",
+              file=sys.stderr)
         return 2
     n_gpus = world if world > 1 else args.gpus
 
@@ -229,7 +280,7 @@ def main() -> int:
             dist.all_gather_object(gathered, real_sched.get("pinned_device"))
             real_sched["rank_devices"] = gathered
 
-    sched = run_sched_bench(args.pods) if rank == 0 else {}
+    sched = run_sched_bench(args.pods) if args.full and rank == 0 else {}
 
     nbytes = args.bytes
     if world > 1:
@@ -260,6 +311,8 @@ def main() -> int:
         ms_per_step = (t1 - t0) / args.steps * 1e3
         value = 2.0 * nbytes * args.steps / (t1 - t0) / 1e9
         mode = "hbm_d2d_copy"
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, dst)
     else:
         # CPU smoke mode (no GPU in CI container): memcpy stand-in so the
         # contract runs end to end; numbers are not MI355X numbers.
@@ -275,6 +328,8 @@ def main() -> int:
         ms_per_step = (t1 - t0) / args.steps * 1e3
         value = 2.0 * nbytes * args.steps / (t1 - t0) / 1e9
         mode = "cpu_smoke_copy"
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, dst)
 
     if rank == 0:
         # honest per-mode labeling (round-1 fix): the k=1 degenerate

@@ -1,5 +1,8 @@
 import os
+import pathlib
+import shutil
 import sys
+import tempfile
 
 import pytest
 
@@ -10,6 +13,19 @@ def pytest_configure(config):
     config.addinivalue_line(
         "markers", "gpu: test requires a real MI355X GPU (run via gpurun)"
     )
+
+
+@pytest.fixture
+def sock_dir():
+    """Short directory for AF_UNIX sockets.
+
+    sun_path holds at most 107 bytes and gRPC refuses longer paths, which a
+    pytest tmp_path under a deep home or TMPDIR exceeds.
+    """
+    base = "/tmp" if os.access("/tmp", os.W_OK | os.X_OK) else None
+    d = tempfile.mkdtemp(prefix="kg-", dir=base)
+    yield pathlib.Path(d)
+    shutil.rmtree(d, ignore_errors=True)
 
 
 @pytest.fixture

@@ -25,7 +25,8 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
-def _run_dist(script: str, nproc: int = 2, timeout: int = 240, extra_env=None):
+def _run_dist(script: str, nproc: int = 2, timeout: int = 240, extra_env=None,
+              bench_args=()):
     env = dict(os.environ)
     env["MASTER_ADDR"] = "127.0.0.1"
     if extra_env:
@@ -36,7 +37,8 @@ def _run_dist(script: str, nproc: int = 2, timeout: int = 240, extra_env=None):
             "--nnodes=1", f"--nproc-per-node={nproc}",
             "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
             script, *(["--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-                       "--pods", "50"] if script.endswith("bench.py") else []),
+                       "--pods", "50", *bench_args]
+                      if script.endswith("bench.py") else []),
         ],
         capture_output=True,
         timeout=timeout,
@@ -48,8 +50,9 @@ def _run_dist(script: str, nproc: int = 2, timeout: int = 240, extra_env=None):
 
 @pytest.mark.timeout(300)
 def test_bench_world2_gloo_contract():
-    """bench.py over 2 gloo ranks prints one valid JSON contract line."""
-    res = _run_dist(os.path.join(REPO, "bench.py"))
+    """bench.py --full over 2 gloo ranks prints one valid JSON contract
+    line, schedule-latency keys included."""
+    res = _run_dist(os.path.join(REPO, "bench.py"), bench_args=("--full",))
     assert res.returncode == 0, res.stderr[-2000:]
     json_lines = [
         l for l in res.stdout.splitlines() if l.startswith("{") and '"metric"' in l
@@ -102,6 +105,34 @@ def test_bench_single_process_contract():
     rec = json.loads(res.stdout.strip().splitlines()[-1])
     assert rec["n_gpus"] == 1 and rec["value"] > 0
     assert rec["metric"] == "scheduled_set_allreduce_busbw_GBps"
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    # the schedule-latency stream is a --full extra, not part of a plain run
+    assert "schedule_p50_ms" not in rec
+
+
+@pytest.mark.timeout(180)
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last step's destination buffer as
+    float32; two runs with the same arguments dump identical arrays."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        res = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"),
+             "--steps", "2", "--warmup", "1", "--bytes", str((5 << 20) + 3),
+             "--dump-outputs", str(out)],
+            capture_output=True, timeout=150, cwd=REPO, text=True,
+        )
+        assert res.returncode == 0, res.stderr[-2000:]
+        dumps.append(np.load(out / "dst.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32
+    # above the whole-buffer limit: a fixed-size sample, well under 64 MB
+    assert a.shape == (4 << 20,)
+    assert np.array_equal(a, b)
+    assert np.all(a == 1.0)  # the copy of an all-ones source
 
 
 def test_bench_gpus_flag_without_ranks_errors():

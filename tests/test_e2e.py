@@ -356,7 +356,7 @@ def test_bind_plan_cache_equivalence():
     assert len(cached.core._plan_cache) > 0  # the cache actually engaged
 
 
-def test_agent_startup_probe_stub(tmp_path, monkeypatch, capsys):
+def test_agent_startup_probe_stub(tmp_path, monkeypatch, capsys, sock_dir):
     """--startup-probe runs the probe binary and exports busbw; verified
     hermetically with a stub probe."""
     import stat
@@ -374,7 +374,7 @@ def test_agent_startup_probe_stub(tmp_path, monkeypatch, capsys):
 
     rc = agent_main([
         "--fake", "--no-register", "--oneshot", "--startup-probe",
-        "--socket", str(tmp_path / "a.sock"), "--metrics-port", "0",
+        "--socket", str(sock_dir / "a.sock"), "--metrics-port", "0",
     ])
     assert rc == 0
     if hasattr(METRICS, "_xgmi"):

@@ -126,7 +126,7 @@ def test_extender_http_roundtrip():
 
 
 @pytest.mark.timeout(120)
-def test_agent_feeds_extender(tmp_path):
+def test_agent_feeds_extender(sock_dir):
     """Deployment loop end to end: the node agent POSTs its inventory to
     the extender every health tick; the extender then scores the node
     for kube-scheduler."""
@@ -142,7 +142,7 @@ def test_agent_feeds_extender(tmp_path):
         proc = subprocess.Popen(
             [sys.executable, "-m", "kubegpu_amd.server.agent",
              "--fake", "--no-register",
-             "--socket", str(tmp_path / "agent.sock"),
+             "--socket", str(sock_dir / "agent.sock"),
              "--metrics-port", "0",
              "--health-interval", "0.2",
              "--extender-url", f"http://127.0.0.1:{port}",

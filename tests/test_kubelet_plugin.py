@@ -16,10 +16,10 @@ def _serialize(m):
 
 
 @pytest.fixture
-def plugin(tmp_path):
+def plugin(sock_dir):
     mgr = create_device_plugin(FakeBackend(fixtures.fixture_2hive_8gpu()))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "amdgpu.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "amdgpu.sock"))
     p.start()
     yield p
     p.stop()
@@ -128,7 +128,7 @@ def test_allocate_unknown_device_rejected(channel):
     assert err.value.code() == grpc.StatusCode.INVALID_ARGUMENT
 
 
-def test_registration_roundtrip(tmp_path):
+def test_registration_roundtrip(sock_dir):
     """Register against a fake kubelet Registration service."""
     from concurrent import futures
 
@@ -148,7 +148,7 @@ def test_registration_roundtrip(tmp_path):
             )
         },
     )
-    kubelet_sock = str(tmp_path / "kubelet.sock")
+    kubelet_sock = str(sock_dir / "kubelet.sock")
     server = grpc.server(futures.ThreadPoolExecutor(max_workers=2))
     server.add_generic_rpc_handlers((handler,))
     server.add_insecure_port(f"unix://{kubelet_sock}")
@@ -156,7 +156,7 @@ def test_registration_roundtrip(tmp_path):
 
     mgr = create_device_plugin(FakeBackend(fixtures.fixture_8x_mi355x()))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "amdgpu.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "amdgpu.sock"))
     p.start()
     p.register_with_kubelet(kubelet_socket=kubelet_sock)
     assert received["req"].resource_name == "amd.com/gpu"
@@ -208,7 +208,7 @@ def test_preferred_allocation_two_musts_both_kept(channel):
     assert len(idx) == 4 and 0 in idx and 5 in idx
 
 
-def test_ecc_unhealthy_device_flagged(tmp_path):
+def test_ecc_unhealthy_device_flagged(sock_dir):
     """A GPU with uncorrectable ECC errors is advertised UNHEALTHY;
     healthy peers stay HEALTHY."""
     from kubegpu_amd.discovery import FakeBackend, fixtures
@@ -217,7 +217,7 @@ def test_ecc_unhealthy_device_flagged(tmp_path):
     fix.devices[3].ecc_uncorrectable = 2
     mgr = create_device_plugin(FakeBackend(fix))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "ecc.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "ecc.sock"))
     p.start()
     try:
         ch = grpc.insecure_channel(f"unix://{p.socket_path}")
@@ -235,7 +235,7 @@ def test_ecc_unhealthy_device_flagged(tmp_path):
         p.stop()
 
 
-def test_vanished_gpu_tombstoned_unhealthy(tmp_path):
+def test_vanished_gpu_tombstoned_unhealthy(sock_dir):
     """A GPU that disappears between discoveries stays advertised as an
     UNHEALTHY device (tombstone) instead of silently shrinking the node."""
     from kubegpu_amd.discovery import FakeBackend, fixtures
@@ -254,7 +254,7 @@ def test_vanished_gpu_tombstoned_unhealthy(tmp_path):
     assert health[gone.uuid] is False
     assert sum(health.values()) == 7
 
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "van.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "van.sock"))
     p.start()
     try:
         ch = grpc.insecure_channel(f"unix://{p.socket_path}")
@@ -274,7 +274,7 @@ def test_vanished_gpu_tombstoned_unhealthy(tmp_path):
         p.stop()
 
 
-def test_register_with_fake_kubelet(tmp_path):
+def test_register_with_fake_kubelet(sock_dir):
     """register_with_kubelet posts a well-formed RegisterRequest to the
     kubelet Registration service (verified against a fake kubelet)."""
     import threading
@@ -291,7 +291,7 @@ def test_register_with_fake_kubelet(tmp_path):
         done.set()
         return dpapi.Empty()
 
-    kubelet_sock = str(tmp_path / "kubelet.sock")
+    kubelet_sock = str(sock_dir / "kubelet.sock")
     server = grpc.server(futures.ThreadPoolExecutor(max_workers=2))
     handler = grpc.method_handlers_generic_handler(
         dpapi.REGISTRATION_SERVICE,
@@ -307,7 +307,7 @@ def test_register_with_fake_kubelet(tmp_path):
     try:
         mgr = create_device_plugin(FakeBackend(fixtures.fixture_8x_mi355x()))
         mgr.start()
-        p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "amdgpu.sock"))
+        p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "amdgpu.sock"))
         p.register_with_kubelet(kubelet_sock)
         assert done.wait(5)
         assert got["version"] == dpapi.VERSION
@@ -318,13 +318,13 @@ def test_register_with_fake_kubelet(tmp_path):
         server.stop(grace=0.5)
 
 
-def test_full_kubelet_protocol_lifecycle(tmp_path):
+def test_full_kubelet_protocol_lifecycle(sock_dir):
     """The complete kubelet<->plugin protocol in sequence: Register ->
     GetDevicePluginOptions -> ListAndWatch -> GetPreferredAllocation ->
     Allocate (the CPU-only 'kind cluster' flow, BASELINE.json config 1)."""
     mgr = create_device_plugin(FakeBackend(fixtures.fixture_2hive_8gpu()))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "life.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "life.sock"))
     p.start()
     try:
         ch = grpc.insecure_channel(f"unix://{p.socket_path}")
@@ -360,7 +360,7 @@ def test_full_kubelet_protocol_lifecycle(tmp_path):
         p.stop()
 
 
-def test_discovery_failure_flips_unhealthy_and_recovers(tmp_path):
+def test_discovery_failure_flips_unhealthy_and_recovers(sock_dir):
     """Backend failing mid-stream: next frame goes all-Unhealthy; a
     recovered backend flips devices back to Healthy."""
     from kubegpu_amd.discovery import Backend, DiscoveryError
@@ -378,7 +378,7 @@ def test_discovery_failure_flips_unhealthy_and_recovers(tmp_path):
     flaky = Flaky(FakeBackend(fixtures.fixture_8x_mi355x()))
     mgr = create_device_plugin(flaky)
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "flaky.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "flaky.sock"))
     # fast re-send cadence: gRPC prefetches the next frame eagerly, so a
     # state change lands 1-2 frames later — poll to the expected state
     p.servicer.health_interval_s = 0.2
@@ -401,12 +401,14 @@ def test_discovery_failure_flips_unhealthy_and_recovers(tmp_path):
         it = iter(stream)
         wait_state(it, dpapi.HEALTHY)
         flaky.fail = True
-        mgr._last_get_time = 0.0  # expire the 5-min discovery cache
+        # expire the 5-min discovery cache (-inf, not 0.0: the monotonic
+        # clock itself is below 300 s on a freshly booted machine)
+        mgr._last_get_time = float("-inf")
         p.servicer.notify()
         bad = wait_state(it, dpapi.UNHEALTHY)
         assert len(bad) == 8  # devices stay visible
         flaky.fail = False
-        mgr._last_get_time = 0.0
+        mgr._last_get_time = float("-inf")
         p.servicer.notify()
         wait_state(it, dpapi.HEALTHY)
         ch.close()
@@ -454,13 +456,13 @@ def test_allocate_empty_request(channel):
     assert "ROCR_VISIBLE_DEVICES" not in cresp.envs
 
 
-def test_preferred_allocation_avoids_down_links(tmp_path):
+def test_preferred_allocation_avoids_down_links(sock_dir):
     """Degraded mesh through the STOCK path: GetPreferredAllocation
     avoids pairs whose xGMI link is down (p2p=false => host-path)."""
     fix = fixtures.fixture_degraded_mesh(missing=((0, 1), (0, 2), (0, 3), (0, 4)))
     mgr = create_device_plugin(FakeBackend(fix))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "deg.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "deg.sock"))
     p.start()
     try:
         ch = grpc.insecure_channel(f"unix://{p.socket_path}")
@@ -630,36 +632,36 @@ class _FakeKubelet:
             os.unlink(self.sock_path)
 
 
-def test_version_rejected_surfaces_registration_error(tmp_path):
+def test_version_rejected_surfaces_registration_error(sock_dir):
     """A kubelet that only speaks another version rejects v1beta1; the
     plugin raises RegistrationError carrying kubelet's message instead
     of an anonymous RpcError."""
     from kubegpu_amd.server.kubelet_plugin import RegistrationError
 
-    kubelet = _FakeKubelet(str(tmp_path / "kubelet.sock"),
+    kubelet = _FakeKubelet(str(sock_dir / "kubelet.sock"),
                            accept_versions=("v1alpha2",))
     kubelet.start()
     try:
         mgr = create_device_plugin(FakeBackend(fixtures.fixture_8x_mi355x()))
         mgr.start()
-        p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "a.sock"))
+        p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "a.sock"))
         with pytest.raises(RegistrationError, match="unsupported API version"):
             p.register_with_kubelet(kubelet.sock_path)
     finally:
         kubelet.stop()
 
 
-def test_reregister_after_kubelet_restart(tmp_path):
+def test_reregister_after_kubelet_restart(sock_dir):
     """Kubelet restart wipes its plugin registry and recreates its
     socket; the watcher notices the new inode and re-registers, and the
     plugin keeps serving Allocate across the restart (VERDICT #9)."""
     import time as _time
 
-    kubelet = _FakeKubelet(str(tmp_path / "kubelet.sock"))
+    kubelet = _FakeKubelet(str(sock_dir / "kubelet.sock"))
     kubelet.start()
     mgr = create_device_plugin(FakeBackend(fixtures.fixture_2hive_8gpu()))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "amdgpu.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "amdgpu.sock"))
     p.start()
     try:
         p.register_with_kubelet(kubelet.sock_path)
@@ -691,13 +693,13 @@ def test_reregister_after_kubelet_restart(tmp_path):
         kubelet.stop()
 
 
-def test_plugin_socket_recreation_race(tmp_path):
+def test_plugin_socket_recreation_race(sock_dir):
     """Restarting the plugin over a stale socket path works, and a new
     client connects to the NEW server instance (stale-socket unlink in
     start()); the old server's socket removal must not kill the new."""
     mgr = create_device_plugin(FakeBackend(fixtures.fixture_8x_mi355x()))
     mgr.start()
-    path = str(tmp_path / "same.sock")
+    path = str(sock_dir / "same.sock")
     p1 = KubeletDevicePlugin(mgr, socket_path=path)
     p1.start()
     # second instance takes over the same path (plugin upgrade pattern)
@@ -715,7 +717,7 @@ def test_plugin_socket_recreation_race(tmp_path):
 
 
 @pytest.mark.timeout(120)
-def test_agent_process_lifecycle_with_fake_kubelet(tmp_path):
+def test_agent_process_lifecycle_with_fake_kubelet(sock_dir):
     """The production entry point end to end as a real process: starts,
     registers with a (fake) kubelet, survives a kubelet restart via the
     watcher, and exits 0 on SIGTERM."""
@@ -724,13 +726,13 @@ def test_agent_process_lifecycle_with_fake_kubelet(tmp_path):
     import sys
     import time as _time
 
-    kubelet = _FakeKubelet(str(tmp_path / "kubelet.sock"))
+    kubelet = _FakeKubelet(str(sock_dir / "kubelet.sock"))
     kubelet.start()
     try:
         proc = subprocess.Popen(
             [sys.executable, "-m", "kubegpu_amd.server.agent",
              "--fake",
-             "--socket", str(tmp_path / "agent.sock"),
+             "--socket", str(sock_dir / "agent.sock"),
              "--kubelet-socket", kubelet.sock_path,
              "--metrics-port", "0",
              "--health-interval", "0.2"],
@@ -759,17 +761,17 @@ def test_agent_process_lifecycle_with_fake_kubelet(tmp_path):
 
 
 @pytest.mark.timeout(120)
-def test_watcher_retries_until_kubelet_accepts(tmp_path):
+def test_watcher_retries_until_kubelet_accepts(sock_dir):
     """A kubelet that comes back up broken (rejecting registrations)
     then recovers: the watcher keeps retrying each tick until accepted
     instead of giving up after the first failure."""
     import time as _time
 
-    kubelet = _FakeKubelet(str(tmp_path / "kubelet.sock"))
+    kubelet = _FakeKubelet(str(sock_dir / "kubelet.sock"))
     kubelet.start()
     mgr = create_device_plugin(FakeBackend(fixtures.fixture_8x_mi355x()))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "w.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "w.sock"))
     p.start()
     try:
         p.register_with_kubelet(kubelet.sock_path)

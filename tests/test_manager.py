@@ -294,7 +294,7 @@ def test_release_uuids_direct():
     assert mgr.in_use_uuids() == [uuids[2]]
 
 
-def test_kubelet_allocate_does_not_touch_in_use(tmp_path):
+def test_kubelet_allocate_does_not_touch_in_use(sock_dir):
     """The v1beta1 path has no deallocate RPC, so the kubelet server
     must not set a flag it can never clear; occupancy there comes from
     amdsmi process_count."""
@@ -304,7 +304,7 @@ def test_kubelet_allocate_does_not_touch_in_use(tmp_path):
 
     mgr = create_device_plugin(FakeBackend(fixtures.fixture_8x_mi355x()))
     mgr.start()
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "k.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "k.sock"))
     p.start()
     try:
         ch = grpc.insecure_channel(f"unix://{p.socket_path}")

@@ -65,8 +65,8 @@ class _FakePodResources:
 
 
 @pytest.fixture
-def kubelet_pr(tmp_path):
-    srv = _FakePodResources(str(tmp_path / "podres.sock"))
+def kubelet_pr(sock_dir):
+    srv = _FakePodResources(str(sock_dir / "podres.sock"))
     srv.start()
     yield srv
     srv.stop()
@@ -111,17 +111,17 @@ def test_reconcile_ignores_other_resources(kubelet_pr):
     assert mgr.in_use_uuids() == []
 
 
-def test_reconcile_absent_socket_is_noop(tmp_path):
+def test_reconcile_absent_socket_is_noop(sock_dir):
     mgr = _mgr()
-    client = pr.PodResourcesClient(str(tmp_path / "missing.sock"))
+    client = pr.PodResourcesClient(str(sock_dir / "missing.sock"))
     assert pr.reconcile_in_use(mgr, client) is None
     assert mgr.in_use_uuids() == []
 
 
-def test_reconcile_survives_rpc_failure(tmp_path):
+def test_reconcile_survives_rpc_failure(sock_dir):
     """Socket exists but nothing serves it: reconcile logs and no-ops."""
     mgr = _mgr()
-    sock = tmp_path / "dead.sock"
+    sock = sock_dir / "dead.sock"
     sock.touch()
     mgr.gpus["GPU-mi355x-01"].in_use = True
     client = pr.PodResourcesClient(str(sock))
@@ -129,7 +129,7 @@ def test_reconcile_survives_rpc_failure(tmp_path):
     assert mgr.in_use_uuids() == ["GPU-mi355x-01"]  # untouched
 
 
-def test_idle_preference_follows_reconciled_state(kubelet_pr, tmp_path):
+def test_idle_preference_follows_reconciled_state(kubelet_pr, sock_dir):
     """End to end: kubelet says hive-1 GPUs are held by a pod; the next
     GetPreferredAllocation prefers the idle hive."""
     from kubegpu_amd.server import KubeletDevicePlugin, dpapi
@@ -142,7 +142,7 @@ def test_idle_preference_follows_reconciled_state(kubelet_pr, tmp_path):
     ]
     pr.reconcile_in_use(mgr, client)
 
-    p = KubeletDevicePlugin(mgr, socket_path=str(tmp_path / "dp.sock"))
+    p = KubeletDevicePlugin(mgr, socket_path=str(sock_dir / "dp.sock"))
     p.start()
     try:
         ch = grpc.insecure_channel(f"unix://{p.socket_path}")
