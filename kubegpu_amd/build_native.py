@@ -5,7 +5,8 @@ Artifacts (all inside the package so they ship with the repo snapshot):
 * csrc/bin/amdsmiinfo   — C++ enumerator over libamd_smi (g++)
 * csrc/bin/rcclprobe    — HIP + librccl all-reduce probe (hipcc, gfx950)
 * _schedcore*.so        — pybind11 scheduler hot path (g++)
-* _ext/_gpuprobe*.so    — torch extension with CDNA4 bandwidth kernels
+* _ext/_gpuprobe*.so    — torch extension with CDNA4 bandwidth and HBM
+                          integrity (memcheck) kernels
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
 Rebuilds are skipped when the artifact is newer than its source.
@@ -82,17 +83,18 @@ def build_gpuprobe(verbose: bool = True) -> str:
     """HIP bandwidth kernels as a torch extension, built into _ext/."""
     os.environ.setdefault("PYTORCH_ROCM_ARCH", GFX_ARCH)
     os.makedirs(EXT_DIR, exist_ok=True)
-    src = os.path.join(CSRC, "gpuprobe.hip")
+    # bandwidth kernels + HBM integrity (memcheck) kernels, one module
+    srcs = [os.path.join(CSRC, "gpuprobe.hip"), os.path.join(CSRC, "memcheck.hip")]
     suffix = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(EXT_DIR, "_gpuprobe" + suffix)
     alt = os.path.join(EXT_DIR, "_gpuprobe.so")
-    if not (_needs_build(out, src) and _needs_build(alt, src)):
+    if not (_needs_build(out, *srcs) and _needs_build(alt, *srcs)):
         return out if os.path.exists(out) else alt
     from torch.utils.cpp_extension import load
 
     load(
         name="_gpuprobe",
-        sources=[src],
+        sources=srcs,
         build_directory=EXT_DIR,
         extra_cflags=["-O3"],
         verbose=verbose,

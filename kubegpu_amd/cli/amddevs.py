@@ -9,6 +9,9 @@ Modes:
                           node and print the chosen GPU set + allocation
   amddevs --probe K       same, then run the in-pod RCCL probe over the set
   amddevs --health        per-GPU health view (ECC totals, tombstones)
+  amddevs --memcheck      HBM integrity probe over the idle GPUs, one child
+                          process per GPU; prints {uuid: result}
+                          (exit 1 = mismatches, 2 = nothing could run)
 """
 
 from __future__ import annotations
@@ -29,7 +32,15 @@ def main(argv=None) -> int:
     p.add_argument("--plugin", action="store_true", help="run the device-plugin path")
     p.add_argument("--schedule", type=int, metavar="K", help="schedule a K-GPU pod")
     p.add_argument("--probe", type=int, metavar="K", help="schedule + RCCL probe")
-    p.add_argument("--bytes", type=int, default=256 << 20)
+    p.add_argument("--bytes", type=int, default=None,
+                   help="probe buffer size (default 256 MiB for --probe, "
+                        "1 GiB for --memcheck)")
+    p.add_argument("--memcheck", action="store_true",
+                   help="run the HBM integrity probe on every GPU this "
+                        "command can see no allocation on")
+    p.add_argument("--memcheck-idle-only", action="store_true",
+                   help="with --memcheck: also skip GPUs that report any "
+                        "compute process (process_count > 0)")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -59,6 +70,37 @@ def main(argv=None) -> int:
             print("no GPUs discovered", file=sys.stderr)
             return 1
         print(cdi_json(mgr._last_info))
+        return 0
+    if args.memcheck:
+        from ..probe.memcheck import (
+            EXIT_CANNOT_RUN,
+            memcheck_round,
+            run_memcheck_subprocess,
+        )
+
+        if args.fake:
+            print("--memcheck needs real GPUs; the --fake fixture backend "
+                  "has no memory to test", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        mgr = create_device_plugin(backend)
+        mgr.start()
+        nbytes = args.bytes if args.bytes is not None else 1 << 30
+        # An operator asked for this run, and a fresh manager has no
+        # allocation view.  Raw process_count is not occupancy (daemons
+        # registered on KFD make a resting node report 1-2), so it only
+        # gates the run on request; the probe takes its buffer from free
+        # VRAM and cannot disturb a running job's data.
+        results = memcheck_round(
+            mgr, run_memcheck_subprocess, None, nbytes,
+            max_process_count=0 if args.memcheck_idle_only else None,
+        )
+        print(json.dumps(results, indent=1))
+        ran = [r for r in results.values() if "mismatched_words" in r]
+        if any(r["mismatched_words"] for r in ran):
+            return 1
+        if not ran:
+            print("memcheck: no idle GPU could be checked", file=sys.stderr)
+            return EXIT_CANNOT_RUN
         return 0
     if args.health:
         mgr = create_device_plugin(backend)
@@ -124,7 +166,8 @@ def main(argv=None) -> int:
         pred = st.scorer.ring_bw(idxs)
         pred = None if pred >= 1e9 else pred
         out, links = probe_with_link_utilization(
-            run_rccl_probe, devices=idxs, nbytes=args.bytes
+            run_rccl_probe, devices=idxs,
+            nbytes=args.bytes if args.bytes is not None else 256 << 20,
         )
         measured = out.get("busbw_gbps")
         print(json.dumps({

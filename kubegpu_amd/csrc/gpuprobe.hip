@@ -291,7 +291,11 @@ double read_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
   return (double)nbytes * iters / sec / 1e9;
 }
 
+// HBM integrity kernels (memcheck.hip, same extension).
+void bind_memcheck(py::module_& m);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  bind_memcheck(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves
   // gRPC from the same process — measured: with the GIL held, every

@@ -1,0 +1,385 @@
+// memcheck — HBM integrity kernels (gfx950), compiled into _gpuprobe.
+//
+// Moving-inversions style memory test built on the same streaming shape
+// as the bandwidth kernels in gpuprobe.hip: 256-thread blocks, 16 B per
+// lane, grid-stride over size_t, nontemporal loads and stores so every
+// pass goes through HBM instead of sitting in L2 / the 256 MiB Infinity
+// Cache.
+//
+// Patterns (v = 64-bit index of a 16 B vector from the buffer's first
+// byte, j = 32-bit word inside it, ids 0..5, odd id = ~(even id)):
+//   0/1 addr     h = fmix32(lo32(v) ^ hi32(v)*0x9E3779B9 ^ seed)
+//                word[j] = rotl32(h, 8j) ^ K[j]
+//   2/3 checker  c = v even ? 0xAAAAAAAA : 0x55555555; word[j] = j even ? c : ~c
+//   4/5 walk1/0  word[j] = 1 << ((4v + j + seed) mod 32)
+// probe/memcheck.py:reference_words is the numpy definition the GPU
+// tests compare against.
+
+#include <torch/extension.h>
+#include <ATen/hip/HIPContext.h>
+#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
+#include <hip/hip_runtime.h>
+
+#include <tuple>
+#include <vector>
+
+#define WAVE 64
+#define BLOCK 256
+// Same defaults as gpuprobe.hip: the fill is a pure write stream (640
+// workgroups), verify-then-fill uses the copy grid (1024).
+#define DEFAULT_COPY_BLOCKS 1024
+#define DEFAULT_WRITE_BLOCKS 640
+// Measured on MI355X at 1 GiB (profiles/memcheck_bw_mi355x.json), all
+// three pattern families alike, beside write 6,190 / read 6,135 / copy
+// 5,490 GB/s in the same process: fill peaks at 640 wg (5,544 GB/s vs
+// 4,767 at 1024) and verify-then-fill at 1024 (5,443 R+W vs 5,059 at
+// 640, 4,792 at 2048), as write and copy do.  Verify alone carries more
+// integer work per load than read_sum_kernel and wants more waves in
+// flight: a plateau from 1280 to 2048 wg (5,534 / 1536: 5,548 / 1792:
+// 5,604 / 5,493) against 5,150 at 1024, 5,155 at 3072, 5,175 at 4096
+// and 3,348 at 512; 1536 = 6 wg per CU sits in its middle.
+#define VERIFY_BLOCKS 1536
+#define N_PATTERNS 6
+#define MAX_RECORDS_LIMIT 4096
+
+typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
+typedef unsigned long long u64;
+
+// Result block in device memory (u64 slots), then max_records records
+// of two u64 each: {word index, expected << 32 | got}.
+#define RES_COUNT 0
+#define RES_FIRST 1
+#define RES_MASK 2
+#define RES_CLAIM 3
+#define RES_HEADER 4
+
+__device__ __forceinline__ unsigned int fmix32(unsigned int h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+__device__ __forceinline__ unsigned int rotl32(unsigned int x, int r) {
+  return (x << r) | (x >> (32 - r));
+}
+
+// FAMILY = pattern id >> 1; inv = all-ones for the odd (complement) id.
+template <int FAMILY>
+__device__ __forceinline__ uint4v pattern_vec(size_t v, unsigned int seed,
+                                              unsigned int inv) {
+  uint4v w;
+  if (FAMILY == 0) {
+    unsigned int lo = (unsigned int)v;
+    unsigned int hi = (unsigned int)((u64)v >> 32);
+    unsigned int h = fmix32(lo ^ (hi * 0x9E3779B9u) ^ seed);
+    w.x = h;
+    w.y = rotl32(h, 8) ^ 0x9E3779B9u;
+    w.z = rotl32(h, 16) ^ 0x7F4A7C15u;
+    w.w = rotl32(h, 24) ^ 0xF39CC060u;
+  } else if (FAMILY == 1) {
+    unsigned int c = (v & 1) ? 0x55555555u : 0xAAAAAAAAu;
+    w.x = c;
+    w.y = ~c;
+    w.z = c;
+    w.w = ~c;
+  } else {
+    // (4v + j + seed) mod 32: 32 divides 2^32, so u32 wraparound is exact
+    unsigned int s = ((unsigned int)v << 2) + seed;
+    w.x = 1u << (s & 31u);
+    w.y = 1u << ((s + 1u) & 31u);
+    w.z = 1u << ((s + 2u) & 31u);
+    w.w = 1u << ((s + 3u) & 31u);
+  }
+  w.x ^= inv;
+  w.y ^= inv;
+  w.z ^= inv;
+  w.w ^= inv;
+  return w;
+}
+
+template <int FAMILY>
+__global__ void fill_pattern_kernel(uint4v* __restrict__ dst, size_t n4,
+                                    unsigned int seed, unsigned int inv) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < n4; i += stride)
+    __builtin_nontemporal_store(pattern_vec<FAMILY>(i, seed, inv), &dst[i]);
+}
+
+// Mismatch path only (never taken on healthy memory): claim a log slot
+// per bad word; slots past max_records are dropped, the count is not.
+__device__ __noinline__ void log_mismatch(u64* __restrict__ res, int max_records,
+                                          u64 word_index, unsigned int expected,
+                                          unsigned int got) {
+  u64 slot = atomicAdd(&res[RES_CLAIM], 1ULL);
+  if (slot < (u64)max_records) {
+    res[RES_HEADER + 2 * slot] = word_index;
+    res[RES_HEADER + 2 * slot + 1] = ((u64)expected << 32) | (u64)got;
+  }
+}
+
+struct Tally {
+  u64 count;
+  u64 first;
+  unsigned int mask;
+};
+
+__device__ __forceinline__ void check_vec(Tally& t, uint4v got, uint4v exp,
+                                          size_t i, u64* __restrict__ res,
+                                          int max_records) {
+  unsigned int dx = got.x ^ exp.x, dy = got.y ^ exp.y;
+  unsigned int dz = got.z ^ exp.z, dw = got.w ^ exp.w;
+  if ((dx | dy | dz | dw) != 0u) {
+    u64 base = (u64)i * 4ULL;
+    // descending j so `first` ends at the lowest bad word of the vector
+    if (dw) { t.count++; if (base + 3 < t.first) t.first = base + 3; log_mismatch(res, max_records, base + 3, exp.w, got.w); }
+    if (dz) { t.count++; if (base + 2 < t.first) t.first = base + 2; log_mismatch(res, max_records, base + 2, exp.z, got.z); }
+    if (dy) { t.count++; if (base + 1 < t.first) t.first = base + 1; log_mismatch(res, max_records, base + 1, exp.y, got.y); }
+    if (dx) { t.count++; if (base < t.first) t.first = base; log_mismatch(res, max_records, base, exp.x, got.x); }
+    t.mask |= dx | dy | dz | dw;
+  }
+}
+
+// Per-thread tallies -> wave shuffle reduce -> LDS block reduce -> one
+// atomic per block per result (the read_sum_kernel shape).
+__device__ __forceinline__ void reduce_tally(Tally t, u64* __restrict__ res) {
+  __shared__ u64 sh_count[BLOCK / WAVE];
+  __shared__ u64 sh_first[BLOCK / WAVE];
+  __shared__ unsigned int sh_mask[BLOCK / WAVE];
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    t.count += __shfl_down(t.count, off, WAVE);
+    u64 f = __shfl_down(t.first, off, WAVE);
+    t.first = f < t.first ? f : t.first;
+    t.mask |= __shfl_down(t.mask, off, WAVE);
+  }
+  int lane = threadIdx.x % WAVE;
+  int wid = threadIdx.x / WAVE;
+  if (lane == 0) {
+    sh_count[wid] = t.count;
+    sh_first[wid] = t.first;
+    sh_mask[wid] = t.mask;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 count = 0, first = ~0ULL;
+    unsigned int mask = 0;
+    for (int w = 0; w < BLOCK / WAVE; ++w) {
+      count += sh_count[w];
+      first = sh_first[w] < first ? sh_first[w] : first;
+      mask |= sh_mask[w];
+    }
+    atomicAdd(&res[RES_COUNT], count);
+    if (count != 0) {
+      atomicMin(&res[RES_FIRST], first);
+      atomicOr(&res[RES_MASK], (u64)mask);
+    }
+  }
+}
+
+template <int FAMILY>
+__global__ void verify_pattern_kernel(const uint4v* __restrict__ src, size_t n4,
+                                      unsigned int seed, unsigned int inv,
+                                      u64* __restrict__ res, int max_records) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  size_t stride = (size_t)gridDim.x * blockDim.x;
+  Tally t = {0, ~0ULL, 0};
+  for (; i < n4; i += stride) {
+    uint4v got = __builtin_nontemporal_load(&src[i]);
+    check_vec(t, got, pattern_vec<FAMILY>(i, seed, inv), i, res, max_records);
+  }
+  reduce_tally(t, res);
+}
+
+// Fused read-check-write pass (the moving-inversions step): every word
+// ends up holding the next pattern whether or not it matched.
+template <int EXPECT_FAMILY, int NEXT_FAMILY>
+__global__ void verify_then_fill_kernel(uint4v* __restrict__ buf, size_t n4,
+                                        unsigned int seed, unsigned int expect_inv,
+                                        unsigned int next_inv,
+                                        u64* __restrict__ res, int max_records) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  size_t stride = (size_t)gridDim.x * blockDim.x;
+  Tally t = {0, ~0ULL, 0};
+  for (; i < n4; i += stride) {
+    uint4v got = __builtin_nontemporal_load(&buf[i]);
+    __builtin_nontemporal_store(pattern_vec<NEXT_FAMILY>(i, seed, next_inv), &buf[i]);
+    check_vec(t, got, pattern_vec<EXPECT_FAMILY>(i, seed, expect_inv), i, res,
+              max_records);
+  }
+  reduce_tally(t, res);
+}
+
+// ---------------------------------------------------------------- host
+
+typedef std::tuple<int64_t, int64_t, int64_t> Record;  // word, expected, got
+typedef std::tuple<int64_t, int64_t, int64_t, std::vector<Record>> VerifyOut;
+
+static size_t check_buf(const at::Tensor& buf, int64_t pattern) {
+  TORCH_CHECK(buf.is_cuda(), "memcheck: tensor must be on GPU");
+  TORCH_CHECK(buf.is_contiguous(), "memcheck: tensor must be contiguous");
+  TORCH_CHECK(buf.nbytes() > 0 && buf.nbytes() % 16 == 0,
+              "memcheck: nbytes must be a positive multiple of 16, got ",
+              buf.nbytes());
+  TORCH_CHECK((uintptr_t)buf.data_ptr() % 16 == 0,
+              "memcheck: tensor storage must be 16-byte aligned");
+  TORCH_CHECK(pattern >= 0 && pattern < N_PATTERNS, "memcheck: pattern id ",
+              pattern, " out of range 0..", N_PATTERNS - 1);
+  return buf.nbytes() / 16;
+}
+
+static int pick_blocks(int64_t blocks_arg, size_t n4, int dflt) {
+  TORCH_CHECK(blocks_arg >= 0 && blocks_arg <= (1 << 20),
+              "memcheck: blocks out of range");
+  if (blocks_arg > 0) return (int)blocks_arg;
+  return (int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, (size_t)dflt);
+}
+
+static unsigned int check_seed(int64_t seed) {
+  TORCH_CHECK(seed >= 0 && seed <= 0xFFFFFFFFLL, "memcheck: seed must be a u32");
+  return (unsigned int)seed;
+}
+
+static at::Tensor make_result(const at::Tensor& buf, int64_t max_records) {
+  TORCH_CHECK(max_records >= 0 && max_records <= MAX_RECORDS_LIMIT,
+              "memcheck: max_records must be in 0..", MAX_RECORDS_LIMIT);
+  at::Tensor res = at::zeros({RES_HEADER + 2 * max_records},
+                             buf.options().dtype(at::kLong));
+  res.select(0, RES_FIRST).fill_(-1);  // u64 max: identity for atomicMin
+  return res;
+}
+
+static VerifyOut read_result(const at::Tensor& res, int64_t max_records,
+                             hipStream_t stream) {
+  C10_HIP_CHECK(hipStreamSynchronize(stream));
+  at::Tensor host = res.cpu();
+  const int64_t* p = host.data_ptr<int64_t>();
+  int64_t claimed = p[RES_CLAIM];
+  int64_t n = claimed < max_records ? claimed : max_records;
+  std::vector<Record> records;
+  records.reserve((size_t)n);
+  for (int64_t r = 0; r < n; ++r) {
+    uint64_t eg = (uint64_t)p[RES_HEADER + 2 * r + 1];
+    records.emplace_back(p[RES_HEADER + 2 * r], (int64_t)(eg >> 32),
+                         (int64_t)(eg & 0xFFFFFFFFULL));
+  }
+  return VerifyOut(p[RES_COUNT], p[RES_FIRST], p[RES_MASK], std::move(records));
+}
+
+void fill_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
+                  int64_t blocks_arg) {
+  size_t n4 = check_buf(buf, pattern);
+  unsigned int seed = check_seed(seed_arg);
+  int blocks = pick_blocks(blocks_arg, n4, DEFAULT_WRITE_BLOCKS);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
+  auto stream = at::hip::getCurrentHIPStream();
+  unsigned int inv = (pattern & 1) ? 0xFFFFFFFFu : 0u;
+  uint4v* p = (uint4v*)buf.data_ptr();
+  switch (pattern >> 1) {
+    case 0:
+      hipLaunchKernelGGL(fill_pattern_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
+                         stream, p, n4, seed, inv);
+      break;
+    case 1:
+      hipLaunchKernelGGL(fill_pattern_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
+                         stream, p, n4, seed, inv);
+      break;
+    default:
+      hipLaunchKernelGGL(fill_pattern_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
+                         stream, p, n4, seed, inv);
+      break;
+  }
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+VerifyOut verify_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
+                         int64_t max_records, int64_t blocks_arg) {
+  size_t n4 = check_buf(buf, pattern);
+  unsigned int seed = check_seed(seed_arg);
+  int blocks = pick_blocks(blocks_arg, n4, VERIFY_BLOCKS);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
+  at::Tensor res = make_result(buf, max_records);
+  auto stream = at::hip::getCurrentHIPStream();
+  unsigned int inv =(pattern & 1) ? 0xFFFFFFFFu : 0u;
+  const uint4v* p = (const uint4v*)buf.data_ptr();
+  u64* r = (u64*)res.data_ptr();
+  int mr = (int)max_records;
+  switch (pattern >> 1) {
+    case 0:
+      hipLaunchKernelGGL(verify_pattern_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
+                         stream, p, n4, seed, inv, r, mr);
+      break;
+    case 1:
+      hipLaunchKernelGGL(verify_pattern_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
+                         stream, p, n4, seed, inv, r, mr);
+      break;
+    default:
+      hipLaunchKernelGGL(verify_pattern_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
+                         stream, p, n4, seed, inv, r, mr);
+      break;
+  }
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return read_result(res, max_records, stream);
+}
+
+#define VTF_LAUNCH(E, N)                                                       \
+  hipLaunchKernelGGL((verify_then_fill_kernel<E, N>), dim3(blocks), dim3(BLOCK), \
+                     0, stream, p, n4, seed, einv, ninv, r, mr)
+#define VTF_NEXT(E)                 \
+  switch (next_pattern >> 1) {      \
+    case 0: VTF_LAUNCH(E, 0); break; \
+    case 1: VTF_LAUNCH(E, 1); break; \
+    default: VTF_LAUNCH(E, 2); break; \
+  }
+
+VerifyOut verify_then_fill(at::Tensor buf, int64_t expect_pattern,
+                           int64_t next_pattern, int64_t seed_arg,
+                           int64_t max_records, int64_t blocks_arg) {
+  size_t n4 = check_buf(buf, expect_pattern);
+  TORCH_CHECK(next_pattern >= 0 && next_pattern < N_PATTERNS,
+              "memcheck: pattern id ", next_pattern, " out of range 0..",
+              N_PATTERNS - 1);
+  unsigned int seed = check_seed(seed_arg);
+  int blocks = pick_blocks(blocks_arg, n4, DEFAULT_COPY_BLOCKS);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
+  at::Tensor res = make_result(buf, max_records);
+  auto stream = at::hip::getCurrentHIPStream();
+  unsigned int einv = (expect_pattern & 1) ? 0xFFFFFFFFu : 0u;
+  unsigned int ninv = (next_pattern & 1) ? 0xFFFFFFFFu : 0u;
+  uint4v* p = (uint4v*)buf.data_ptr();
+  u64* r = (u64*)res.data_ptr();
+  int mr = (int)max_records;
+  switch (expect_pattern >> 1) {
+    case 0: VTF_NEXT(0); break;
+    case 1: VTF_NEXT(1); break;
+    default: VTF_NEXT(2); break;
+  }
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return read_result(res, max_records, stream);
+}
+
+#undef VTF_NEXT
+#undef VTF_LAUNCH
+
+// Called from gpuprobe.hip's PYBIND11_MODULE. The GIL is released for
+// the same reason as the timed probes: a pass over a large buffer plus
+// the stream synchronise must not starve the agent's gRPC threads.
+void bind_memcheck(py::module_& m) {
+  m.def("fill_pattern", &fill_pattern, "NT fill with a memcheck pattern",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("buf"), py::arg("pattern"), py::arg("seed"),
+        py::arg("blocks") = 0);
+  m.def("verify_pattern", &verify_pattern,
+        "verify a memcheck pattern -> (mismatched_words, first_bad_word, "
+        "bad_bits_mask, records)",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("buf"), py::arg("pattern"), py::arg("seed"),
+        py::arg("max_records") = 16, py::arg("blocks") = 0);
+  m.def("verify_then_fill", &verify_then_fill,
+        "fused verify(expect_pattern) + fill(next_pattern) pass",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("buf"), py::arg("expect_pattern"), py::arg("next_pattern"),
+        py::arg("seed"), py::arg("max_records") = 16, py::arg("blocks") = 0);
+}

@@ -88,6 +88,10 @@ class AMDGPUManager(Device):
         # allocatable 0) instead of silently shrinking the node, until
         # the grace window expires: uuid -> (last GpuInfo, swept-at).
         self.vanished: Dict[str, tuple] = {}
+        # Active HBM integrity (memcheck) verdicts: uuid -> verdict dict.
+        # Kept here, not on GpuInfo, because GpuInfo objects are replaced
+        # on every re-discovery and the verdict must outlive them.
+        self.memcheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -179,6 +183,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
+                    self.memcheck.pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
             self.bdf_to_id = {g.bdf: u for u, g in self.gpus.items() if g.bdf}
@@ -190,14 +195,57 @@ class AMDGPUManager(Device):
         """uuid -> healthy for every advertisable device.
 
         Present GPUs are healthy unless they report uncorrectable ECC
-        errors (GpuInfo.healthy); tombstoned (recently-vanished) GPUs
-        stay visible but always unhealthy so kubelet degrades
-        allocatable instead of the node silently shrinking."""
+        errors (GpuInfo.healthy) or carry a failed memcheck verdict;
+        tombstoned (recently-vanished) GPUs stay visible but always
+        unhealthy so kubelet degrades allocatable instead of the node
+        silently shrinking."""
         with self._lock:
-            out = {u: g.healthy for u, g in self.gpus.items()}
+            out = {u: self._gpu_healthy(g) for u, g in self.gpus.items()}
             for u in self.vanished:
                 out.setdefault(u, False)
             return out
+
+    # -- active HBM integrity verdicts ---------------------------------------
+
+    def _gpu_healthy(self, gpu: GpuInfo) -> bool:
+        """ECC health AND no failed memcheck verdict (lock held)."""
+        v = self.memcheck.get(gpu.uuid)
+        return gpu.healthy and (v is None or v["ok"])
+
+    def record_memcheck(self, uuid: str, result: dict) -> bool:
+        """Store a memcheck result (MemcheckResult.to_dict()) for a GPU.
+
+        A result with mismatched words marks the GPU unhealthy until a
+        later passing result or clear_memcheck(); returns the verdict's
+        ok flag.  Unknown uuids are rejected with KeyError."""
+        mismatched = int(result.get("mismatched_words", 0))
+        ok = bool(result.get("ok", mismatched == 0)) and mismatched == 0
+        verdict = dict(result)
+        verdict["ok"] = ok
+        verdict["mismatched_words"] = mismatched
+        verdict.setdefault("timestamp", time.time())
+        with self._lock:
+            if uuid not in self.gpus and uuid not in self.vanished:
+                raise KeyError(f"unknown GPU uuid {uuid}")
+            self.memcheck[uuid] = verdict
+        if not ok:
+            utils.errorf(
+                "memcheck FAILED on GPU %s: %d mismatched word(s), first bad "
+                "offset %s, bad bits 0x%08x — marking Unhealthy",
+                uuid, mismatched, verdict.get("first_bad_offset"),
+                int(verdict.get("bad_bits_mask") or 0),
+            )
+        return ok
+
+    def clear_memcheck(self, uuid: str) -> bool:
+        """Forget a GPU's verdict (operator override); True if one existed."""
+        with self._lock:
+            return self.memcheck.pop(uuid, None) is not None
+
+    def memcheck_status(self, uuid: str) -> Optional[dict]:
+        with self._lock:
+            v = self.memcheck.get(uuid)
+            return dict(v) if v is not None else None
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:
@@ -274,11 +322,11 @@ class AMDGPUManager(Device):
             return
         with self._lock:
             # capacity counts every discovered GPU; allocatable excludes
-            # ECC-unhealthy ones (a GPU with uncorrectable errors stays
+            # ECC-unhealthy and memcheck-failed ones (such a GPU stays
             # visible but must not take new pods — mirrors the kubelet
             # plugin's per-device Unhealthy advertisement)
             count = len(self.gpus)
-            healthy_count = sum(1 for g in self.gpus.values() if g.healthy)
+            healthy_count = sum(1 for g in self.gpus.values() if self._gpu_healthy(g))
             for rl in (node_info.capacity, node_info.kube_cap):
                 rl[RESOURCE_GPU] = count
             for rl in (node_info.allocatable, node_info.kube_alloc):
@@ -291,7 +339,7 @@ class AMDGPUManager(Device):
                 add_group_resource(
                     node_info.capacity, f"{gpu.name}/memory", gpu.memory.vram_total_bytes
                 )
-                if not gpu.healthy:
+                if not self._gpu_healthy(gpu):
                     continue
                 add_group_resource(node_info.allocatable, f"{gpu.name}/cards", 1)
                 add_group_resource(

@@ -33,6 +33,8 @@ class Metrics:
         self.failures = 0
         self.gpu_health: Dict[str, bool] = {}
         self.gpu_in_use: Dict[str, bool] = {}
+        self.gpu_memcheck: Dict[str, dict] = {}
+        self.gpu_memcheck_errors: Dict[str, int] = {}
         if _HAVE_PROM:
             # per-instance registry: multiple Metrics objects (tests,
             # embedded schedulers) must not collide in the global one
@@ -57,7 +59,7 @@ class Metrics:
             )
             self._gpu_health = Gauge(
                 "kubegpu_amd_gpu_healthy",
-                "1 = GPU healthy, 0 = unhealthy (ECC/vanished)",
+                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -70,6 +72,30 @@ class Metrics:
             self._gpu_in_use = Gauge(
                 "kubegpu_amd_gpu_in_use",
                 "1 = GPU held by a live allocation (manager path)",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._memcheck_words = Gauge(
+                "kubegpu_amd_gpu_memcheck_mismatched_words",
+                "32-bit words that read back wrong in the last HBM memcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._memcheck_gbps = Gauge(
+                "kubegpu_amd_gpu_memcheck_gbps",
+                "throughput of the last HBM memcheck, GB/s",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._memcheck_ts = Gauge(
+                "kubegpu_amd_gpu_memcheck_last_run_timestamp_seconds",
+                "unix time of the last completed HBM memcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._memcheck_err = Counter(
+                "kubegpu_amd_gpu_memcheck_errors_total",
+                "HBM memcheck runs that could not complete (not a memory fault)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -108,6 +134,25 @@ class Metrics:
             self.gpu_in_use[uuid] = in_use
         if _HAVE_PROM:
             self._gpu_in_use.labels(uuid=uuid).set(1.0 if in_use else 0.0)
+
+    def set_gpu_memcheck(self, uuid: str, mismatched_words: int, gbps: float,
+                         timestamp: float) -> None:
+        with self._lock:
+            self.gpu_memcheck[uuid] = {
+                "mismatched_words": int(mismatched_words),
+                "gbps": float(gbps),
+                "timestamp": float(timestamp),
+            }
+        if _HAVE_PROM:
+            self._memcheck_words.labels(uuid=uuid).set(float(mismatched_words))
+            self._memcheck_gbps.labels(uuid=uuid).set(float(gbps))
+            self._memcheck_ts.labels(uuid=uuid).set(float(timestamp))
+
+    def inc_memcheck_error(self, uuid: str) -> None:
+        with self._lock:
+            self.gpu_memcheck_errors[uuid] = self.gpu_memcheck_errors.get(uuid, 0) + 1
+        if _HAVE_PROM:
+            self._memcheck_err.labels(uuid=uuid).inc()
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

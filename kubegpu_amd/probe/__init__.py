@@ -13,3 +13,26 @@ from .xgmi_counters import (  # noqa: F401
     probe_with_link_utilization,
     read_link_metrics,
 )
+
+# HBM integrity probe (probe/memcheck.py), re-exported lazily so that
+# `python -m kubegpu_amd.probe.memcheck` runs the module exactly once.
+# The memcheck() function itself shares its name with the submodule, so
+# it is reached as `kubegpu_amd.probe.memcheck.memcheck`.
+_MEMCHECK_EXPORTS = (
+    "MemcheckResult",
+    "VerifyResult",
+    "fill_pattern",
+    "memcheck_round",
+    "reference_words",
+    "run_memcheck_subprocess",
+    "verify_pattern",
+    "verify_then_fill",
+)
+
+
+def __getattr__(name):
+    if name in _MEMCHECK_EXPORTS:
+        from . import memcheck as _memcheck
+
+        return getattr(_memcheck, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

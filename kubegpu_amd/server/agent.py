@@ -55,6 +55,17 @@ def main(argv=None) -> int:
                          "GPUs at start and export the measured busbw "
                          "(the verification loop, BASELINE.json)")
     ap.add_argument("--probe-bytes", type=int, default=256 << 20)
+    ap.add_argument("--memcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the HBM integrity probe over the idle GPUs "
+                         "every SECONDS from the health loop; a GPU with "
+                         "mismatches turns Unhealthy (0 = off)")
+    ap.add_argument("--memcheck-bytes", type=int, default=1 << 30,
+                    help="buffer size per GPU for the HBM integrity probe")
+    ap.add_argument("--memcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the HBM integrity probe; set it to the "
+                         "node's resting value when daemons hold KFD open")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -108,6 +119,7 @@ def main(argv=None) -> int:
         return 0
 
     watcher_started = False
+    next_memcheck = time.monotonic()  # first round on the first tick
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -155,6 +167,20 @@ def main(argv=None) -> int:
             reconcile_in_use(manager, client)
         except Exception as e:  # never let reconcile kill the agent
             utils.logf(2, "agent: pod-resources reconcile error: %s", e)
+        # active HBM integrity probe: one child process per idle GPU,
+        # after reconcile so in_use is current; a failed verdict flips
+        # device_health(), so wake ListAndWatch again afterwards
+        if args.memcheck_interval > 0 and time.monotonic() >= next_memcheck:
+            next_memcheck = time.monotonic() + args.memcheck_interval
+            try:
+                from ..probe.memcheck import memcheck_round, run_memcheck_subprocess
+
+                memcheck_round(manager, run_memcheck_subprocess, METRICS,
+                               args.memcheck_bytes,
+                               max_process_count=args.memcheck_max_procs)
+            except Exception as e:  # never let the probe kill the agent
+                utils.errorf("agent: memcheck round failed: %s", e)
+            plugin.servicer.notify()
         for uuid, ok in manager.device_health().items():
             g = manager.gpu_or_tombstone(uuid)
             METRICS.set_gpu_health(
