@@ -14,7 +14,10 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <hip/hip_runtime.h>
+
+#include <cstdint>
 
 #define WAVE 64
 #define BLOCK 256
@@ -142,22 +145,107 @@ __global__ void fill_kernel_v4_nt(uint4v* __restrict__ dst, size_t n4,
   for (; i < n4; i += stride) __builtin_nontemporal_store(v, &dst[i]);
 }
 
+// ---------------------------------------------------------------- host
+
+#define MAX_BLOCKS (1 << 20)
+
+static void check_buf(const at::Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), "gpuprobe: tensors must be on GPU");
+  TORCH_CHECK(t.is_contiguous(), "gpuprobe: tensors must be contiguous");
+}
+
+// A 16 B/lane kernel needs a positive whole number of vectors at a
+// 16-byte-aligned address; returns that number.
+static size_t check_vec_buf(const at::Tensor& t) {
+  check_buf(t);
+  TORCH_CHECK(t.nbytes() > 0 && t.nbytes() % 16 == 0,
+              "gpuprobe: nbytes must be a positive multiple of 16, got ", t.nbytes());
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0,
+              "gpuprobe: tensor storage must be 16-byte aligned");
+  return t.nbytes() / 16;
+}
+
+// The kernels take __restrict__ pointers: the same range twice is fine
+// (every lane reads an element before it writes that element), two
+// ranges that overlap in part are not.
 static void check_pair(const at::Tensor& dst, const at::Tensor& src) {
-  TORCH_CHECK(src.is_cuda() && dst.is_cuda(), "gpuprobe: tensors must be on GPU");
-  TORCH_CHECK(src.is_contiguous() && dst.is_contiguous(),
-              "gpuprobe: tensors must be contiguous");
+  check_buf(dst);
+  check_buf(src);
   TORCH_CHECK(src.nbytes() == dst.nbytes(), "gpuprobe: size mismatch");
+  TORCH_CHECK(src.device() == dst.device(),
+              "gpuprobe: tensors must be on the same device");
+  uintptr_t s = (uintptr_t)src.data_ptr(), d = (uintptr_t)dst.data_ptr();
+  size_t n = src.nbytes();
+  TORCH_CHECK(s == d || s + n <= d || d + n <= s,
+              "gpuprobe: dst and src overlap in part");
+}
+
+static int check_threads(int64_t threads_arg) {
+  TORCH_CHECK(threads_arg >= 0 && threads_arg % WAVE == 0 && threads_arg <= 1024,
+              "threads: multiple of 64, <=1024");
+  return threads_arg > 0 ? (int)threads_arg : BLOCK;
+}
+
+static int pick_blocks(int64_t blocks_arg, size_t n4, int threads, int dflt) {
+  TORCH_CHECK(blocks_arg >= 0 && blocks_arg <= MAX_BLOCKS,
+              "gpuprobe: blocks out of range 0..", MAX_BLOCKS);
+  if (blocks_arg > 0) return (int)blocks_arg;
+  return (int)std::min<size_t>((n4 + threads - 1) / threads, (size_t)dflt);
+}
+
+static void check_variant(int64_t variant) {
+  TORCH_CHECK(variant >= 0 && variant <= 3, "gpuprobe: variant ", variant,
+              " out of range 0..3");
+}
+
+// The one place each kernel is launched from: the timed probes and the
+// untimed entry points below both go through these, so what the tests
+// compare with a reference is what the probes time.
+static void launch_copy(const void* src, void* dst, size_t n4, int64_t variant,
+                        bool nontemporal, int blocks, int threads,
+                        hipStream_t stream) {
+  if (variant == 1)
+    hipLaunchKernelGGL(copy_kernel_v4_nt_u4, dim3(blocks), dim3(threads), 0, stream,
+                       (const uint4v*)src, (uint4v*)dst, n4);
+  else if (variant == 2)
+    hipLaunchKernelGGL(copy_kernel_v4_nt_chunk, dim3(blocks), dim3(threads), 0,
+                       stream, (const uint4v*)src, (uint4v*)dst, n4);
+  else if (variant == 3)
+    hipLaunchKernelGGL(copy_kernel_v4_mixed, dim3(blocks), dim3(threads), 0,
+                       stream, (const uint4v*)src, (uint4v*)dst, n4);
+  else if (nontemporal)
+    hipLaunchKernelGGL(copy_kernel_v4_nt, dim3(blocks), dim3(threads), 0, stream,
+                       (const uint4v*)src, (uint4v*)dst, n4);
+  else
+    hipLaunchKernelGGL(copy_kernel_v4, dim3(blocks), dim3(threads), 0, stream,
+                       (const uint4*)src, (uint4*)dst, n4);
+}
+
+// read_sum_kernel sizes its LDS array for BLOCK threads.
+static void launch_read_sum(const void* src, size_t n4, void* out, int blocks,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(read_sum_kernel, dim3(blocks), dim3(BLOCK), 0, stream,
+                     (const uint4*)src, n4, (unsigned long long*)out);
+}
+
+static void launch_fill(void* dst, size_t n4, unsigned int word, int blocks,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL(fill_kernel_v4_nt, dim3(blocks), dim3(BLOCK), 0, stream,
+                     (uint4v*)dst, n4, word);
 }
 
 void copy(at::Tensor dst, at::Tensor src) {
   check_pair(dst, src);
   size_t nbytes = src.nbytes();
+  if (nbytes == 0) return;
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(dst));
   auto stream = at::hip::getCurrentHIPStream();
-  if (nbytes % 16 == 0) {
+  // 16 B vectors only for a whole number of them at aligned addresses;
+  // a view at a 4-byte offset goes to the byte kernel like an odd size
+  if ((((uintptr_t)src.data_ptr() | (uintptr_t)dst.data_ptr() | nbytes) & 15) == 0) {
     size_t n4 = nbytes / 16;
     int blocks = (int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, DEFAULT_COPY_BLOCKS);
-    hipLaunchKernelGGL(copy_kernel_v4_nt, dim3(blocks), dim3(BLOCK), 0, stream,
-                       (const uint4v*)src.data_ptr(), (uint4v*)dst.data_ptr(), n4);
+    launch_copy(src.data_ptr(), dst.data_ptr(), n4, 0, true, blocks, BLOCK, stream);
   } else {
     int blocks = (int)std::min<size_t>((nbytes + BLOCK - 1) / BLOCK, 4096);
     hipLaunchKernelGGL(copy_kernel_b, dim3(blocks), dim3(BLOCK), 0, stream,
@@ -167,43 +255,80 @@ void copy(at::Tensor dst, at::Tensor src) {
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+// One untimed launch of a copy_bw_gbps variant on the caller's tensors
+// (same kernel selection, same default grid).
+void copy_variant(at::Tensor dst, at::Tensor src, int64_t variant, bool nontemporal,
+                  int64_t blocks_arg, int64_t threads_arg) {
+  check_pair(dst, src);
+  size_t n4 = check_vec_buf(src);
+  check_vec_buf(dst);
+  check_variant(variant);
+  int threads = check_threads(threads_arg);
+  int blocks = pick_blocks(blocks_arg, n4, threads, DEFAULT_COPY_BLOCKS);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(dst));
+  auto stream = at::hip::getCurrentHIPStream();
+  launch_copy(src.data_ptr(), dst.data_ptr(), n4, variant, nontemporal, blocks,
+              threads, stream);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// One launch of read_sum_kernel into a fresh accumulator: the sum of
+// all 32-bit words of src, modulo 2^64.
+uint64_t read_sum(at::Tensor src, int64_t blocks_arg) {
+  size_t n4 = check_vec_buf(src);
+  int blocks = pick_blocks(blocks_arg, n4, BLOCK, DEFAULT_COPY_BLOCKS);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(src));
+  at::Tensor out = at::zeros({1}, src.options().dtype(at::kLong));
+  auto stream = at::hip::getCurrentHIPStream();
+  launch_read_sum(src.data_ptr(), n4, out.data_ptr(), blocks, stream);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  C10_HIP_CHECK(hipStreamSynchronize(stream));
+  return (uint64_t)out.item<int64_t>();
+}
+
+// One launch of fill_kernel_v4_nt: every 32-bit word of dst = word.
+void fill_word(at::Tensor dst, int64_t word, int64_t blocks_arg) {
+  size_t n4 = check_vec_buf(dst);
+  TORCH_CHECK(word >= 0 && word <= 0xFFFFFFFFLL, "gpuprobe: word must be a u32");
+  int blocks = pick_blocks(blocks_arg, n4, BLOCK, DEFAULT_WRITE_BLOCKS);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(dst));
+  auto stream = at::hip::getCurrentHIPStream();
+  launch_fill(dst.data_ptr(), n4, (unsigned int)word, blocks, stream);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+static void check_timed_args(int64_t nbytes, int64_t iters) {
+  TORCH_CHECK(nbytes > 0 && nbytes % 16 == 0, "nbytes must be positive, 16-aligned");
+  TORCH_CHECK(iters >= 1, "iters must be at least 1");
+}
+
+// Byte the timed probes put into a destination before the first launch.
+// The caching allocator often hands back the block that the previous
+// probe freed, still full of the "expected" 0x01 bytes: without this a
+// kernel that wrote nothing would pass the self-check.
+#define POISON 0xA5
+
 // Timed device-to-device streaming copy; returns achieved GB/s
 // (bytes read + bytes written over wall time, hipEvent-timed).
 // blocks=0 picks the default; nontemporal selects the NT variant.
 double copy_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg,
                     bool nontemporal, int64_t variant, int64_t threads_arg) {
-  TORCH_CHECK(nbytes > 0 && nbytes % 16 == 0, "nbytes must be positive, 16-aligned");
+  check_timed_args(nbytes, iters);
+  check_variant(variant);
+  size_t n4 = (size_t)nbytes / 16;
+  // workgroup SIZE is a runtime launch dim (the kernels read blockDim),
+  // so the wave-granularity axis can be swept without new kernels
+  int threads = check_threads(threads_arg);
+  int blocks = pick_blocks(blocks_arg, n4, threads, DEFAULT_COPY_BLOCKS);
   auto opts = at::TensorOptions().dtype(at::kByte).device(at::kCUDA);
   at::Tensor src = at::empty({nbytes}, opts);
   at::Tensor dst = at::empty({nbytes}, opts);
   src.fill_(1);
+  dst.fill_(POISON);
   auto stream = at::hip::getCurrentHIPStream();
-  size_t n4 = (size_t)nbytes / 16;
-  // workgroup SIZE is a runtime launch dim (the kernels read blockDim),
-  // so the wave-granularity axis can be swept without new kernels
-  int threads = threads_arg > 0 ? (int)threads_arg : BLOCK;
-  TORCH_CHECK(threads % WAVE == 0 && threads <= 1024, "threads: multiple of 64, <=1024");
-  int blocks = blocks_arg > 0
-                   ? (int)blocks_arg
-                   : (int)std::min<size_t>((n4 + threads - 1) / threads, DEFAULT_COPY_BLOCKS);
   auto launch = [&]() {
-    if (variant == 1)
-      hipLaunchKernelGGL(copy_kernel_v4_nt_u4, dim3(blocks), dim3(threads), 0, stream,
-                         (const uint4v*)src.data_ptr(), (uint4v*)dst.data_ptr(), n4);
-    else if (variant == 2)
-      hipLaunchKernelGGL(copy_kernel_v4_nt_chunk, dim3(blocks), dim3(threads), 0,
-                         stream, (const uint4v*)src.data_ptr(),
-                         (uint4v*)dst.data_ptr(), n4);
-    else if (variant == 3)
-      hipLaunchKernelGGL(copy_kernel_v4_mixed, dim3(blocks), dim3(threads), 0,
-                         stream, (const uint4v*)src.data_ptr(),
-                         (uint4v*)dst.data_ptr(), n4);
-    else if (nontemporal)
-      hipLaunchKernelGGL(copy_kernel_v4_nt, dim3(blocks), dim3(threads), 0, stream,
-                         (const uint4v*)src.data_ptr(), (uint4v*)dst.data_ptr(), n4);
-    else
-      hipLaunchKernelGGL(copy_kernel_v4, dim3(blocks), dim3(threads), 0, stream,
-                         (const uint4*)src.data_ptr(), (uint4*)dst.data_ptr(), n4);
+    launch_copy(src.data_ptr(), dst.data_ptr(), n4, variant, nontemporal, blocks,
+                threads, stream);
   };
   for (int w = 0; w < 3; ++w) launch();
   hipEvent_t t0, t1;
@@ -225,17 +350,47 @@ double copy_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg,
 }
 
 double write_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
-  TORCH_CHECK(nbytes > 0 && nbytes % 16 == 0, "nbytes must be positive, 16-aligned");
+  check_timed_args(nbytes, iters);
+  size_t n4 = (size_t)nbytes / 16;
+  int blocks = pick_blocks(blocks_arg, n4, BLOCK, DEFAULT_WRITE_BLOCKS);
   auto opts = at::TensorOptions().dtype(at::kByte).device(at::kCUDA);
   at::Tensor dst = at::empty({nbytes}, opts);
+  dst.fill_(POISON);
   auto stream = at::hip::getCurrentHIPStream();
+  auto launch = [&]() { launch_fill(dst.data_ptr(), n4, 0x01010101u, blocks, stream); };
+  for (int w = 0; w < 3; ++w) launch();
+  hipEvent_t t0, t1;
+  (void)hipEventCreate(&t0);
+  (void)hipEventCreate(&t1);
+  (void)hipEventRecord(t0, stream);
+  for (int64_t i = 0; i < iters; ++i) launch();
+  (void)hipEventRecord(t1, stream);
+  (void)hipEventSynchronize(t1);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, t0, t1);
+  (void)hipEventDestroy(t0);
+  (void)hipEventDestroy(t1);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  // every byte is 0x01 iff min == max == 1 (a sum alone is met by
+  // other contents too)
+  TORCH_CHECK(dst.min().item<uint8_t>() == 1 && dst.max().item<uint8_t>() == 1,
+              "write_bw_gbps: fill produced wrong output");
+  return (double)nbytes * iters / (ms / 1e3) / 1e9;
+}
+
+double read_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
+  check_timed_args(nbytes, iters);
   size_t n4 = (size_t)nbytes / 16;
-  int blocks = blocks_arg > 0
-                   ? (int)blocks_arg
-                   : (int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, DEFAULT_WRITE_BLOCKS);
+  // Reads peak at 1024 wg (4 waves/CU): 6,115 GB/s vs 5,768 at 4096
+  // (profiles/read_bw_sweep_mi355x.json)
+  int blocks = pick_blocks(blocks_arg, n4, BLOCK, DEFAULT_COPY_BLOCKS);
+  auto opts = at::TensorOptions().dtype(at::kByte).device(at::kCUDA);
+  at::Tensor src = at::empty({nbytes}, opts);
+  src.fill_(1);
+  at::Tensor out = at::zeros({1}, at::TensorOptions().dtype(at::kLong).device(at::kCUDA));
+  auto stream = at::hip::getCurrentHIPStream();
   auto launch = [&]() {
-    hipLaunchKernelGGL(fill_kernel_v4_nt, dim3(blocks), dim3(BLOCK), 0, stream,
-                       (uint4v*)dst.data_ptr(), n4, 0x01010101u);
+    launch_read_sum(src.data_ptr(), n4, out.data_ptr(), blocks, stream);
   };
   for (int w = 0; w < 3; ++w) launch();
   hipEvent_t t0, t1;
@@ -250,43 +405,11 @@ double write_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
   (void)hipEventDestroy(t0);
   (void)hipEventDestroy(t1);
   C10_HIP_KERNEL_LAUNCH_CHECK();
-  TORCH_CHECK((int64_t)dst.sum(at::kLong).item<int64_t>() == nbytes,
-              "write_bw_gbps: fill produced wrong output");
-  return (double)nbytes * iters / (ms / 1e3) / 1e9;
-}
-
-double read_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
-  TORCH_CHECK(nbytes > 0 && nbytes % 16 == 0, "nbytes must be positive, 16-aligned");
-  auto opts = at::TensorOptions().dtype(at::kByte).device(at::kCUDA);
-  at::Tensor src = at::empty({nbytes}, opts);
-  src.fill_(1);
-  at::Tensor out = at::zeros({1}, at::TensorOptions().dtype(at::kLong).device(at::kCUDA));
-  auto stream = at::hip::getCurrentHIPStream();
-  size_t n4 = (size_t)nbytes / 16;
-  // Reads peak at 1024 wg (4 waves/CU): 6,115 GB/s vs 5,768 at 4096
-  // (profiles/read_bw_sweep_mi355x.json)
-  int blocks = blocks_arg > 0
-                   ? (int)blocks_arg
-                   : (int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, DEFAULT_COPY_BLOCKS);
-  for (int w = 0; w < 3; ++w)
-    hipLaunchKernelGGL(read_sum_kernel, dim3(blocks), dim3(BLOCK), 0, stream,
-                       (const uint4*)src.data_ptr(), n4,
-                       (unsigned long long*)out.data_ptr());
-  hipEvent_t t0, t1;
-  (void)hipEventCreate(&t0);
-  (void)hipEventCreate(&t1);
-  (void)hipEventRecord(t0, stream);
-  for (int64_t i = 0; i < iters; ++i)
-    hipLaunchKernelGGL(read_sum_kernel, dim3(blocks), dim3(BLOCK), 0, stream,
-                       (const uint4*)src.data_ptr(), n4,
-                       (unsigned long long*)out.data_ptr());
-  (void)hipEventRecord(t1, stream);
-  (void)hipEventSynchronize(t1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  C10_HIP_KERNEL_LAUNCH_CHECK();
+  // every launch adds the whole buffer's words to out: a kernel that
+  // read less would report too high a bandwidth
+  uint64_t want = (uint64_t)(3 + iters) * ((uint64_t)nbytes / 4) * 0x01010101ULL;
+  TORCH_CHECK((uint64_t)out.item<int64_t>() == want,
+              "read_bw_gbps: read_sum_kernel produced a wrong sum");
   double sec = ms / 1e3;
   return (double)nbytes * iters / sec / 1e9;
 }
@@ -302,6 +425,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // concurrent RPC hit DEADLINE_EXCEEDED during a probe block).
   m.def("copy", &copy, "streaming uint4 copy kernel (dst, src)",
         py::call_guard<py::gil_scoped_release>());
+  m.def("copy_variant", &copy_variant,
+        "one untimed launch of a copy_bw_gbps variant (dst, src)",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("dst"), py::arg("src"), py::arg("variant") = 0,
+        py::arg("nontemporal") = true, py::arg("blocks") = 0,
+        py::arg("threads") = 0);
+  m.def("read_sum", &read_sum, "u64 sum of all 32-bit words (one launch)",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("src"), py::arg("blocks") = 0);
+  m.def("fill_word", &fill_word, "NT fill of every 32-bit word (one launch)",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("dst"), py::arg("word"), py::arg("blocks") = 0);
   m.def("copy_bw_gbps", &copy_bw_gbps, "timed d2d copy bandwidth",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("nbytes"), py::arg("iters") = 20, py::arg("blocks") = 0,

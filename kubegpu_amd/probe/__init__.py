@@ -2,9 +2,12 @@
 
 from .bandwidth import (  # noqa: F401
     copy,
+    copy_variant,
     d2d_copy_bw_gbps,
+    fill_word,
     load_ext,
     read_bw_gbps,
+    read_sum,
     write_bw_gbps,
 )
 from .rccl_probe import run_rccl_probe, torch_allreduce_busbw  # noqa: F401

@@ -50,6 +50,34 @@ def copy(dst, src) -> None:
     load_ext().copy(dst, src)
 
 
+def copy_variant(
+    dst,
+    src,
+    variant: int = 0,
+    nontemporal: bool = True,
+    blocks: int = 0,
+    threads: int = 0,
+) -> None:
+    """One untimed launch of a d2d_copy_bw_gbps kernel on dst/src.
+
+    Same kernel selection and default grid as the timed probe. Both
+    tensors must be 16-byte aligned with nbytes a multiple of 16.
+    """
+    load_ext().copy_variant(dst, src, variant, nontemporal, blocks, threads)
+
+
+def read_sum(src, blocks: int = 0) -> int:
+    """Sum of all 32-bit words of src modulo 2**64 (one launch of the
+    read_bw_gbps kernel into a zeroed accumulator)."""
+    return load_ext().read_sum(src, blocks)
+
+
+def fill_word(dst, word: int, blocks: int = 0) -> None:
+    """Set every 32-bit word of dst to word (one launch of the
+    write_bw_gbps kernel)."""
+    load_ext().fill_word(dst, word, blocks)
+
+
 def d2d_copy_bw_gbps(
     nbytes: int = 1 << 30,
     iters: int = 20,

@@ -103,7 +103,8 @@ def test_gpuprobe_copy_numerics():
 
     ext = load_ext(required=True)
     torch.manual_seed(0)
-    for n in (1 << 10, (1 << 20) + 4, 1 << 24):  # incl. non-16B-aligned
+    # (1 << 20) + 3 floats: nbytes % 16 == 12, the byte-kernel path
+    for n in (1 << 10, (1 << 20) + 4, (1 << 20) + 3, 1 << 24):
         src = torch.randn(n, dtype=torch.float32, device="cuda")
         dst = torch.full_like(src, -1.0)
         ext.copy(dst, src)

@@ -48,7 +48,8 @@ SURFACE = {
     "kubegpu_amd.probe.rccl_probe": ["run_rccl_probe",
         "torch_allreduce_busbw"],
     "kubegpu_amd.probe.bandwidth": ["load_ext", "copy", "d2d_copy_bw_gbps",
-        "read_bw_gbps", "write_bw_gbps"],
+        "read_bw_gbps", "write_bw_gbps", "copy_variant", "read_sum",
+        "fill_word"],
     "kubegpu_amd.probe.xgmi_counters": ["read_link_metrics",
         "diff_link_metrics", "probe_with_link_utilization"],
     "kubegpu_amd.cli.amddevs": ["main"],
