@@ -5,8 +5,9 @@ Artifacts (all inside the package so they ship with the repo snapshot):
 * csrc/bin/amdsmiinfo   — C++ enumerator over libamd_smi (g++)
 * csrc/bin/rcclprobe    — HIP + librccl all-reduce probe (hipcc, gfx950)
 * _schedcore*.so        — pybind11 scheduler hot path (g++)
-* _ext/_gpuprobe*.so    — torch extension with CDNA4 bandwidth and HBM
-                          integrity (memcheck) kernels
+* _ext/_gpuprobe*.so    — torch extension with CDNA4 bandwidth, HBM
+                          integrity (memcheck) and compute-unit
+                          integrity (cucheck) kernels
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
 Rebuilds are skipped when the artifact is newer than its source.
@@ -83,8 +84,10 @@ def build_gpuprobe(verbose: bool = True) -> str:
     """HIP bandwidth kernels as a torch extension, built into _ext/."""
     os.environ.setdefault("PYTORCH_ROCM_ARCH", GFX_ARCH)
     os.makedirs(EXT_DIR, exist_ok=True)
-    # bandwidth kernels + HBM integrity (memcheck) kernels, one module
-    srcs = [os.path.join(CSRC, "gpuprobe.hip"), os.path.join(CSRC, "memcheck.hip")]
+    # bandwidth kernels + HBM integrity (memcheck) kernels + compute-unit
+    # integrity (cucheck) kernel, one module
+    srcs = [os.path.join(CSRC, name)
+            for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip")]
     suffix = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(EXT_DIR, "_gpuprobe" + suffix)
     alt = os.path.join(EXT_DIR, "_gpuprobe.so")

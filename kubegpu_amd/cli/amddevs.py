@@ -12,6 +12,8 @@ Modes:
   amddevs --memcheck      HBM integrity probe over the idle GPUs, one child
                           process per GPU; prints {uuid: result}
                           (exit 1 = mismatches, 2 = nothing could run)
+  amddevs --cucheck       compute-unit integrity probe over the idle GPUs,
+                          same shape and exit codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -41,6 +43,12 @@ def main(argv=None) -> int:
     p.add_argument("--memcheck-idle-only", action="store_true",
                    help="with --memcheck: also skip GPUs that report any "
                         "compute process (process_count > 0)")
+    p.add_argument("--cucheck", action="store_true",
+                   help="run the compute-unit integrity probe on every GPU "
+                        "this command can see no allocation on")
+    p.add_argument("--rounds", type=int, default=None, metavar="N",
+                   help="with --cucheck: rounds per GPU (default: the "
+                        "probe's own, about 0.5 s)")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -100,6 +108,35 @@ def main(argv=None) -> int:
             return 1
         if not ran:
             print("memcheck: no idle GPU could be checked", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        return 0
+    if args.cucheck:
+        from ..probe.cucheck import (
+            DEFAULT_ROUNDS,
+            EXIT_CANNOT_RUN,
+            cucheck_round,
+            run_cucheck_subprocess,
+        )
+
+        if args.fake:
+            print("--cucheck needs real GPUs; the --fake fixture backend "
+                  "has no compute units to test", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        mgr = create_device_plugin(backend)
+        mgr.start()
+        # as for --memcheck: an operator asked, and raw process_count is
+        # not occupancy, so it does not gate the run
+        results = cucheck_round(
+            mgr, run_cucheck_subprocess, None,
+            args.rounds if args.rounds is not None else DEFAULT_ROUNDS,
+            max_process_count=None,
+        )
+        print(json.dumps(results, indent=1))
+        ran = [r for r in results.values() if "mismatches" in r]
+        if any(r["mismatches"] for r in ran):
+            return 1
+        if not ran:
+            print("cucheck: no idle GPU could be checked", file=sys.stderr)
             return EXIT_CANNOT_RUN
         return 0
     if args.health:

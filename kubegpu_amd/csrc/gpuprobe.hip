@@ -416,9 +416,12 @@ double read_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
 
 // HBM integrity kernels (memcheck.hip, same extension).
 void bind_memcheck(py::module_& m);
+// Compute-unit integrity kernel (cucheck.hip, same extension).
+void bind_cucheck(py::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_memcheck(m);
+  bind_cucheck(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves
   // gRPC from the same process — measured: with the GIL held, every

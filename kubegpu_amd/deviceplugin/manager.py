@@ -92,6 +92,8 @@ class AMDGPUManager(Device):
         # Kept here, not on GpuInfo, because GpuInfo objects are replaced
         # on every re-discovery and the verdict must outlive them.
         self.memcheck: Dict[str, dict] = {}
+        # Active compute-unit integrity (cucheck) verdicts, kept the same way.
+        self.cucheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -184,6 +186,7 @@ class AMDGPUManager(Device):
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
                     self.memcheck.pop(uuid, None)
+                    self.cucheck.pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
             self.bdf_to_id = {g.bdf: u for u, g in self.gpus.items() if g.bdf}
@@ -195,7 +198,8 @@ class AMDGPUManager(Device):
         """uuid -> healthy for every advertisable device.
 
         Present GPUs are healthy unless they report uncorrectable ECC
-        errors (GpuInfo.healthy) or carry a failed memcheck verdict;
+        errors (GpuInfo.healthy) or carry a failed memcheck or cucheck
+        verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -208,9 +212,10 @@ class AMDGPUManager(Device):
     # -- active HBM integrity verdicts ---------------------------------------
 
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
-        """ECC health AND no failed memcheck verdict (lock held)."""
-        v = self.memcheck.get(gpu.uuid)
-        return gpu.healthy and (v is None or v["ok"])
+        """ECC health AND no failed memcheck or cucheck verdict (lock held)."""
+        m = self.memcheck.get(gpu.uuid)
+        c = self.cucheck.get(gpu.uuid)
+        return gpu.healthy and (m is None or m["ok"]) and (c is None or c["ok"])
 
     def record_memcheck(self, uuid: str, result: dict) -> bool:
         """Store a memcheck result (MemcheckResult.to_dict()) for a GPU.
@@ -245,6 +250,44 @@ class AMDGPUManager(Device):
     def memcheck_status(self, uuid: str) -> Optional[dict]:
         with self._lock:
             v = self.memcheck.get(uuid)
+            return dict(v) if v is not None else None
+
+    # -- active compute-unit integrity verdicts ---------------------------------
+
+    def record_cucheck(self, uuid: str, result: dict) -> bool:
+        """Store a cucheck result (CucheckResult.to_dict()) for a GPU.
+
+        A result with mismatches marks the GPU unhealthy until a later
+        passing result or clear_cucheck(); returns the verdict's ok
+        flag.  Unknown uuids are rejected with KeyError."""
+        mismatches = int(result.get("mismatches", 0))
+        ok = bool(result.get("ok", mismatches == 0)) and mismatches == 0
+        verdict = dict(result)
+        verdict["ok"] = ok
+        verdict["mismatches"] = mismatches
+        verdict.setdefault("timestamp", time.time())
+        with self._lock:
+            if uuid not in self.gpus and uuid not in self.vanished:
+                raise KeyError(f"unknown GPU uuid {uuid}")
+            self.cucheck[uuid] = verdict
+        if not ok:
+            utils.errorf(
+                "cucheck FAILED on GPU %s: %d wrong digest(s), first bad round "
+                "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
+                uuid, mismatches, verdict.get("first_bad_round"),
+                ",".join(verdict.get("bad_stages") or []) or "?",
+                ",".join(verdict.get("bad_cus") or []) or "?",
+            )
+        return ok
+
+    def clear_cucheck(self, uuid: str) -> bool:
+        """Forget a GPU's verdict (operator override); True if one existed."""
+        with self._lock:
+            return self.cucheck.pop(uuid, None) is not None
+
+    def cucheck_status(self, uuid: str) -> Optional[dict]:
+        with self._lock:
+            v = self.cucheck.get(uuid)
             return dict(v) if v is not None else None
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
@@ -322,9 +365,9 @@ class AMDGPUManager(Device):
             return
         with self._lock:
             # capacity counts every discovered GPU; allocatable excludes
-            # ECC-unhealthy and memcheck-failed ones (such a GPU stays
-            # visible but must not take new pods — mirrors the kubelet
-            # plugin's per-device Unhealthy advertisement)
+            # ECC-unhealthy, memcheck-failed and cucheck-failed ones (such
+            # a GPU stays visible but must not take new pods — mirrors the
+            # kubelet plugin's per-device Unhealthy advertisement)
             count = len(self.gpus)
             healthy_count = sum(1 for g in self.gpus.values() if self._gpu_healthy(g))
             for rl in (node_info.capacity, node_info.kube_cap):

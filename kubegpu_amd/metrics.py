@@ -35,6 +35,8 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         self.gpu_memcheck: Dict[str, dict] = {}
         self.gpu_memcheck_errors: Dict[str, int] = {}
+        self.gpu_cucheck: Dict[str, dict] = {}
+        self.gpu_cucheck_errors: Dict[str, int] = {}
         if _HAVE_PROM:
             # per-instance registry: multiple Metrics objects (tests,
             # embedded schedulers) must not collide in the global one
@@ -59,7 +61,7 @@ class Metrics:
             )
             self._gpu_health = Gauge(
                 "kubegpu_amd_gpu_healthy",
-                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck)",
+                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -96,6 +98,30 @@ class Metrics:
             self._memcheck_err = Counter(
                 "kubegpu_amd_gpu_memcheck_errors_total",
                 "HBM memcheck runs that could not complete (not a memory fault)",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._cucheck_mismatches = Gauge(
+                "kubegpu_amd_gpu_cucheck_mismatches",
+                "wave digests that came out wrong in the last compute-unit cucheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._cucheck_cus = Gauge(
+                "kubegpu_amd_gpu_cucheck_cus_covered",
+                "distinct compute units that ran a wave of the last cucheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._cucheck_ts = Gauge(
+                "kubegpu_amd_gpu_cucheck_last_run_timestamp_seconds",
+                "unix time of the last completed compute-unit cucheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._cucheck_err = Counter(
+                "kubegpu_amd_gpu_cucheck_errors_total",
+                "cucheck runs that could not complete (not a compute fault)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -153,6 +179,25 @@ class Metrics:
             self.gpu_memcheck_errors[uuid] = self.gpu_memcheck_errors.get(uuid, 0) + 1
         if _HAVE_PROM:
             self._memcheck_err.labels(uuid=uuid).inc()
+
+    def set_gpu_cucheck(self, uuid: str, mismatches: int, cus_covered: int,
+                        timestamp: float) -> None:
+        with self._lock:
+            self.gpu_cucheck[uuid] = {
+                "mismatches": int(mismatches),
+                "cus_covered": int(cus_covered),
+                "timestamp": float(timestamp),
+            }
+        if _HAVE_PROM:
+            self._cucheck_mismatches.labels(uuid=uuid).set(float(mismatches))
+            self._cucheck_cus.labels(uuid=uuid).set(float(cus_covered))
+            self._cucheck_ts.labels(uuid=uuid).set(float(timestamp))
+
+    def inc_cucheck_error(self, uuid: str) -> None:
+        with self._lock:
+            self.gpu_cucheck_errors[uuid] = self.gpu_cucheck_errors.get(uuid, 0) + 1
+        if _HAVE_PROM:
+            self._cucheck_err.labels(uuid=uuid).inc()
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

@@ -33,9 +33,24 @@ _MEMCHECK_EXPORTS = (
 )
 
 
+# Compute-unit integrity probe (probe/cucheck.py), the same way; the
+# cucheck() function is `kubegpu_amd.probe.cucheck.cucheck`.
+_CUCHECK_EXPORTS = (
+    "CucheckResult",
+    "cucheck_round",
+    "reference_digests",
+    "run_cucheck_subprocess",
+    "wave_digests",
+)
+
+
 def __getattr__(name):
     if name in _MEMCHECK_EXPORTS:
         from . import memcheck as _memcheck
 
         return getattr(_memcheck, name)
+    if name in _CUCHECK_EXPORTS:
+        from . import cucheck as _cucheck
+
+        return getattr(_cucheck, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -289,7 +289,7 @@ def memcheck(
 # -- child process -----------------------------------------------------------
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-_child_lock = threading.Lock()  # one memcheck child at a time
+_child_lock = threading.Lock()  # one active-probe child at a time (cucheck too)
 
 
 def run_memcheck_subprocess(index: int, nbytes: int = DEFAULT_BYTES,
@@ -316,6 +316,20 @@ def run_memcheck_subprocess(index: int, nbytes: int = DEFAULT_BYTES,
     return rec
 
 
+def idle_gpus(manager, max_process_count: Optional[int]) -> List[Tuple[int, str]]:
+    """(index, uuid) of every present GPU an active probe may take, in
+    index order: no allocation, and process_count at most
+    max_process_count (None ignores process_count).  Shared with the
+    compute-unit probe (probe/cucheck.py)."""
+    with manager._lock:
+        return sorted(
+            (g.index, u) for u, g in manager.gpus.items()
+            if not g.in_use and (
+                max_process_count is None or g.process_count <= max_process_count
+            )
+        )
+
+
 def memcheck_round(manager, runner: Callable[[int, int], dict], metrics=None,
                    nbytes: int = DEFAULT_BYTES,
                    max_process_count: Optional[int] = 0) -> Dict[str, dict]:
@@ -333,13 +347,7 @@ def memcheck_round(manager, runner: Callable[[int, int], dict], metrics=None,
     GPU's health is left as it was.  Returns {uuid: result}."""
     from ..api import utils
 
-    with manager._lock:
-        idle = sorted(
-            (g.index, u) for u, g in manager.gpus.items()
-            if not g.in_use and (
-                max_process_count is None or g.process_count <= max_process_count
-            )
-        )
+    idle = idle_gpus(manager, max_process_count)
     out: Dict[str, dict] = {}
     for index, uuid in idle:
         try:

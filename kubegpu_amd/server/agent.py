@@ -66,6 +66,17 @@ def main(argv=None) -> int:
                     help="highest amdsmi process_count still treated as "
                          "idle by the HBM integrity probe; set it to the "
                          "node's resting value when daemons hold KFD open")
+    ap.add_argument("--cucheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the compute-unit integrity probe over the idle "
+                         "GPUs every SECONDS from the health loop; a GPU "
+                         "with a wrong digest turns Unhealthy (0 = off)")
+    ap.add_argument("--cucheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the compute-unit integrity "
+                         "probe (default: the probe's own, about 0.5 s)")
+    ap.add_argument("--cucheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the compute-unit integrity probe")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -120,6 +131,7 @@ def main(argv=None) -> int:
 
     watcher_started = False
     next_memcheck = time.monotonic()  # first round on the first tick
+    next_cucheck = time.monotonic()
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -180,6 +192,23 @@ def main(argv=None) -> int:
                                max_process_count=args.memcheck_max_procs)
             except Exception as e:  # never let the probe kill the agent
                 utils.errorf("agent: memcheck round failed: %s", e)
+            plugin.servicer.notify()
+        # active compute-unit integrity probe, same shape; its children
+        # share memcheck's lock, so the two never overlap on a GPU
+        if args.cucheck_interval > 0 and time.monotonic() >= next_cucheck:
+            next_cucheck = time.monotonic() + args.cucheck_interval
+            try:
+                from ..probe.cucheck import (
+                    DEFAULT_ROUNDS,
+                    cucheck_round,
+                    run_cucheck_subprocess,
+                )
+
+                cucheck_round(manager, run_cucheck_subprocess, METRICS,
+                              args.cucheck_rounds or DEFAULT_ROUNDS,
+                              max_process_count=args.cucheck_max_procs)
+            except Exception as e:  # never let the probe kill the agent
+                utils.errorf("agent: cucheck round failed: %s", e)
             plugin.servicer.notify()
         for uuid, ok in manager.device_health().items():
             g = manager.gpu_or_tombstone(uuid)
