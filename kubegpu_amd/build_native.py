@@ -6,11 +6,14 @@ Artifacts (all inside the package so they ship with the repo snapshot):
 * csrc/bin/rcclprobe    — HIP + librccl all-reduce probe (hipcc, gfx950)
 * _schedcore*.so        — pybind11 scheduler hot path (g++)
 * _ext/_gpuprobe*.so    — torch extension with CDNA4 bandwidth, HBM
-                          integrity (memcheck) and compute-unit
-                          integrity (cucheck) kernels
+                          integrity (memcheck), compute-unit integrity
+                          (cucheck) and host-link integrity (hostlink)
+                          kernels; memcheck and hostlink share
+                          csrc/pattern_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
-Rebuilds are skipped when the artifact is newer than its source.
+Rebuilds are skipped when the artifact is newer than its sources, the
+shared header included.
 """
 
 from __future__ import annotations
@@ -85,13 +88,17 @@ def build_gpuprobe(verbose: bool = True) -> str:
     os.environ.setdefault("PYTORCH_ROCM_ARCH", GFX_ARCH)
     os.makedirs(EXT_DIR, exist_ok=True)
     # bandwidth kernels + HBM integrity (memcheck) kernels + compute-unit
-    # integrity (cucheck) kernel, one module
+    # integrity (cucheck) kernel + host-link integrity (hostlink)
+    # kernels, one module
     srcs = [os.path.join(CSRC, name)
-            for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip")]
+            for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip",
+                         "hostlink.hip")]
+    # included, not compiled: only the staleness check needs to see them
+    deps = srcs + [os.path.join(CSRC, "pattern_common.h")]
     suffix = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(EXT_DIR, "_gpuprobe" + suffix)
     alt = os.path.join(EXT_DIR, "_gpuprobe.so")
-    if not (_needs_build(out, *srcs) and _needs_build(alt, *srcs)):
+    if not (_needs_build(out, *deps) and _needs_build(alt, *deps)):
         return out if os.path.exists(out) else alt
     from torch.utils.cpp_extension import load
 

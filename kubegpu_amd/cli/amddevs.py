@@ -14,6 +14,9 @@ Modes:
                           (exit 1 = mismatches, 2 = nothing could run)
   amddevs --cucheck       compute-unit integrity probe over the idle GPUs,
                           same shape and exit codes ([--rounds N])
+  amddevs --hostlink      host-link (PCIe path) integrity and bandwidth
+                          probe over the idle GPUs, same shape and exit
+                          codes ([--bytes N])
 """
 
 from __future__ import annotations
@@ -36,7 +39,7 @@ def main(argv=None) -> int:
     p.add_argument("--probe", type=int, metavar="K", help="schedule + RCCL probe")
     p.add_argument("--bytes", type=int, default=None,
                    help="probe buffer size (default 256 MiB for --probe, "
-                        "1 GiB for --memcheck)")
+                        "1 GiB for --memcheck, 256 MiB for --hostlink)")
     p.add_argument("--memcheck", action="store_true",
                    help="run the HBM integrity probe on every GPU this "
                         "command can see no allocation on")
@@ -49,6 +52,9 @@ def main(argv=None) -> int:
     p.add_argument("--rounds", type=int, default=None, metavar="N",
                    help="with --cucheck: rounds per GPU (default: the "
                         "probe's own, about 0.5 s)")
+    p.add_argument("--hostlink", action="store_true",
+                   help="run the host-link integrity and bandwidth probe on "
+                        "every GPU this command can see no allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -137,6 +143,35 @@ def main(argv=None) -> int:
             return 1
         if not ran:
             print("cucheck: no idle GPU could be checked", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        return 0
+    if args.hostlink:
+        from ..probe.hostlink import (
+            DEFAULT_BYTES,
+            EXIT_CANNOT_RUN,
+            hostlink_round,
+            run_hostlink_subprocess,
+        )
+
+        if args.fake:
+            print("--hostlink needs real GPUs; the --fake fixture backend "
+                  "has no host link to test", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        mgr = create_device_plugin(backend)
+        mgr.start()
+        # as for --memcheck: an operator asked, and raw process_count is
+        # not occupancy, so it does not gate the run
+        results = hostlink_round(
+            mgr, run_hostlink_subprocess, None,
+            args.bytes if args.bytes is not None else DEFAULT_BYTES,
+            max_process_count=None,
+        )
+        print(json.dumps(results, indent=1))
+        ran = [r for r in results.values() if "mismatched_words" in r]
+        if any(r["mismatched_words"] or r.get("cpu_sample_mismatches") for r in ran):
+            return 1
+        if not ran:
+            print("hostlink: no idle GPU could be checked", file=sys.stderr)
             return EXIT_CANNOT_RUN
         return 0
     if args.health:

@@ -94,6 +94,8 @@ class AMDGPUManager(Device):
         self.memcheck: Dict[str, dict] = {}
         # Active compute-unit integrity (cucheck) verdicts, kept the same way.
         self.cucheck: Dict[str, dict] = {}
+        # Active host-link integrity (hostlink) verdicts, kept the same way.
+        self.hostlink: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -187,6 +189,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                     self.memcheck.pop(uuid, None)
                     self.cucheck.pop(uuid, None)
+                    self.hostlink.pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
             self.bdf_to_id = {g.bdf: u for u, g in self.gpus.items() if g.bdf}
@@ -198,8 +201,8 @@ class AMDGPUManager(Device):
         """uuid -> healthy for every advertisable device.
 
         Present GPUs are healthy unless they report uncorrectable ECC
-        errors (GpuInfo.healthy) or carry a failed memcheck or cucheck
-        verdict;
+        errors (GpuInfo.healthy) or carry a failed memcheck, cucheck or
+        hostlink verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -212,10 +215,13 @@ class AMDGPUManager(Device):
     # -- active HBM integrity verdicts ---------------------------------------
 
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
-        """ECC health AND no failed memcheck or cucheck verdict (lock held)."""
+        """ECC health AND no failed memcheck, cucheck or hostlink verdict
+        (lock held)."""
         m = self.memcheck.get(gpu.uuid)
         c = self.cucheck.get(gpu.uuid)
-        return gpu.healthy and (m is None or m["ok"]) and (c is None or c["ok"])
+        h = self.hostlink.get(gpu.uuid)
+        return gpu.healthy and (m is None or m["ok"]) and (c is None or c["ok"]) \
+            and (h is None or h["ok"])
 
     def record_memcheck(self, uuid: str, result: dict) -> bool:
         """Store a memcheck result (MemcheckResult.to_dict()) for a GPU.
@@ -288,6 +294,51 @@ class AMDGPUManager(Device):
     def cucheck_status(self, uuid: str) -> Optional[dict]:
         with self._lock:
             v = self.cucheck.get(uuid)
+            return dict(v) if v is not None else None
+
+    # -- active host-link integrity verdicts -------------------------------------
+
+    def record_hostlink(self, uuid: str, result: dict) -> bool:
+        """Store a hostlink result (HostlinkResult.to_dict()) for a GPU.
+
+        A result with words that arrived wrong (found by the GPU or by
+        the CPU's sample) marks the GPU unhealthy until a later passing
+        result or clear_hostlink(); a bandwidth figure below the floor
+        (below_floor) does not.  Returns the verdict's ok flag.  Unknown
+        uuids are rejected with KeyError."""
+        mismatched = int(result.get("mismatched_words", 0))
+        sampled = int(result.get("cpu_sample_mismatches", 0))
+        bad = mismatched + sampled
+        ok = bool(result.get("ok", bad == 0)) and bad == 0
+        verdict = dict(result)
+        verdict["ok"] = ok
+        verdict["mismatched_words"] = mismatched
+        verdict["cpu_sample_mismatches"] = sampled
+        verdict.setdefault("timestamp", time.time())
+        with self._lock:
+            if uuid not in self.gpus and uuid not in self.vanished:
+                raise KeyError(f"unknown GPU uuid {uuid}")
+            self.hostlink[uuid] = verdict
+        if not ok:
+            first = (verdict.get("records") or [{}])[0]
+            utils.errorf(
+                "hostlink FAILED on GPU %s: %d mismatched word(s) seen by the GPU, "
+                "%d by the CPU sample; first record in pass %s (%s), first bad "
+                "offset %s, bad bits 0x%08x — marking Unhealthy",
+                uuid, mismatched, sampled, first.get("pass", "?"),
+                first.get("path", "?"), verdict.get("first_bad_offset"),
+                int(verdict.get("bad_bits_mask") or 0),
+            )
+        return ok
+
+    def clear_hostlink(self, uuid: str) -> bool:
+        """Forget a GPU's verdict (operator override); True if one existed."""
+        with self._lock:
+            return self.hostlink.pop(uuid, None) is not None
+
+    def hostlink_status(self, uuid: str) -> Optional[dict]:
+        with self._lock:
+            v = self.hostlink.get(uuid)
             return dict(v) if v is not None else None
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
@@ -365,8 +416,8 @@ class AMDGPUManager(Device):
             return
         with self._lock:
             # capacity counts every discovered GPU; allocatable excludes
-            # ECC-unhealthy, memcheck-failed and cucheck-failed ones (such
-            # a GPU stays visible but must not take new pods — mirrors the
+            # ECC-unhealthy, memcheck-failed, cucheck-failed and
+            # hostlink-failed ones (such a GPU stays visible but must not take new pods — mirrors the
             # kubelet plugin's per-device Unhealthy advertisement)
             count = len(self.gpus)
             healthy_count = sum(1 for g in self.gpus.values() if self._gpu_healthy(g))

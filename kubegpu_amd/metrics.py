@@ -37,6 +37,8 @@ class Metrics:
         self.gpu_memcheck_errors: Dict[str, int] = {}
         self.gpu_cucheck: Dict[str, dict] = {}
         self.gpu_cucheck_errors: Dict[str, int] = {}
+        self.gpu_hostlink: Dict[str, dict] = {}
+        self.gpu_hostlink_errors: Dict[str, int] = {}
         if _HAVE_PROM:
             # per-instance registry: multiple Metrics objects (tests,
             # embedded schedulers) must not collide in the global one
@@ -61,7 +63,7 @@ class Metrics:
             )
             self._gpu_health = Gauge(
                 "kubegpu_amd_gpu_healthy",
-                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck)",
+                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck/hostlink)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -122,6 +124,45 @@ class Metrics:
             self._cucheck_err = Counter(
                 "kubegpu_amd_gpu_cucheck_errors_total",
                 "cucheck runs that could not complete (not a compute fault)",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._hostlink_words = Gauge(
+                "kubegpu_amd_gpu_hostlink_mismatches",
+                "32-bit words that crossed the host link wrong in the last hostlink",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._hostlink_h2d = Gauge(
+                "kubegpu_amd_gpu_hostlink_h2d_gbps",
+                "host-to-device bandwidth of GPU loads from pinned host memory "
+                "in the last hostlink, GB/s",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._hostlink_d2h = Gauge(
+                "kubegpu_amd_gpu_hostlink_d2h_gbps",
+                "device-to-host bandwidth of GPU stores to pinned host memory "
+                "in the last hostlink, GB/s",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._hostlink_floor = Gauge(
+                "kubegpu_amd_gpu_hostlink_below_floor",
+                "1 = a one-way figure of the last hostlink was under the "
+                "configured floor (health unaffected)",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._hostlink_ts = Gauge(
+                "kubegpu_amd_gpu_hostlink_last_run_timestamp_seconds",
+                "unix time of the last completed hostlink",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._hostlink_err = Counter(
+                "kubegpu_amd_gpu_hostlink_errors_total",
+                "hostlink runs that could not complete (not a link fault)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -198,6 +239,29 @@ class Metrics:
             self.gpu_cucheck_errors[uuid] = self.gpu_cucheck_errors.get(uuid, 0) + 1
         if _HAVE_PROM:
             self._cucheck_err.labels(uuid=uuid).inc()
+
+    def set_gpu_hostlink(self, uuid: str, mismatches: int, h2d_gbps: float,
+                         d2h_gbps: float, below_floor: bool, timestamp: float) -> None:
+        with self._lock:
+            self.gpu_hostlink[uuid] = {
+                "mismatches": int(mismatches),
+                "h2d_gbps": float(h2d_gbps),
+                "d2h_gbps": float(d2h_gbps),
+                "below_floor": bool(below_floor),
+                "timestamp": float(timestamp),
+            }
+        if _HAVE_PROM:
+            self._hostlink_words.labels(uuid=uuid).set(float(mismatches))
+            self._hostlink_h2d.labels(uuid=uuid).set(float(h2d_gbps))
+            self._hostlink_d2h.labels(uuid=uuid).set(float(d2h_gbps))
+            self._hostlink_floor.labels(uuid=uuid).set(1.0 if below_floor else 0.0)
+            self._hostlink_ts.labels(uuid=uuid).set(float(timestamp))
+
+    def inc_hostlink_error(self, uuid: str) -> None:
+        with self._lock:
+            self.gpu_hostlink_errors[uuid] = self.gpu_hostlink_errors.get(uuid, 0) + 1
+        if _HAVE_PROM:
+            self._hostlink_err.labels(uuid=uuid).inc()
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

@@ -44,6 +44,18 @@ _CUCHECK_EXPORTS = (
 )
 
 
+# Host-link integrity and bandwidth probe (probe/hostlink.py), the same
+# way; the hostlink() function is `kubegpu_amd.probe.hostlink.hostlink`.
+# Its fill_pattern / verify_pattern take host tensors and stay in the
+# submodule: the package-level names are memcheck's.
+_HOSTLINK_EXPORTS = (
+    "HostlinkResult",
+    "hostlink_round",
+    "read_pcie_link",
+    "run_hostlink_subprocess",
+)
+
+
 def __getattr__(name):
     if name in _MEMCHECK_EXPORTS:
         from . import memcheck as _memcheck
@@ -53,4 +65,8 @@ def __getattr__(name):
         from . import cucheck as _cucheck
 
         return getattr(_cucheck, name)
+    if name in _HOSTLINK_EXPORTS:
+        from . import hostlink as _hostlink
+
+        return getattr(_hostlink, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,550 @@
+"""Active host-link integrity and bandwidth probe — wrapper over the
+hostlink HIP kernels.
+
+``memcheck`` asks whether HBM returns what was written and ``cucheck``
+whether the compute units return right answers; this asks the same of
+the path between the GPU and host memory: the PCIe endpoint, the root
+port or switch above it, the IOMMU mapping, the runtime's copy path and
+the host DRAM behind it.  ``hostlink()`` moves the memcheck patterns
+over that path in both directions, with kernels that load and store
+pinned host memory directly and with the runtime's own copies, and
+reports every 32-bit word that arrived wrong together with the
+bandwidth each way.
+
+The patterns are memcheck's, unchanged; ``memcheck.reference_words``
+is the one numpy definition (csrc/pattern_common.h on the GPU side).
+
+What a verdict means: PCIe protects each link with its own CRC and
+replay, so wrong data over a healthy link is rare; a mismatch is a
+statement about the whole GPU-to-host path, not about one lane.  The
+bandwidth figures describe the link as it was trained and loaded at
+that moment — an idle GPU does not mean an idle host — so a figure
+under ``min_gbps`` is reported (``below_floor``) and never makes a GPU
+unhealthy.
+
+CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
+    python -m kubegpu_amd.probe.hostlink --device INDEX [--bytes N]
+        [--seed S] [--min-gbps X]
+"""
+
+from __future__ import annotations
+
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+from dataclasses import dataclass, field
+from typing import Callable, Dict, List, Optional
+
+from .memcheck import (
+    EXIT_CANNOT_RUN,
+    EXIT_MISMATCH,
+    EXIT_PASS,
+    _REPO_ROOT,
+    Pattern,
+    VerifyResult,
+    _child_lock,
+    _to_result,
+    idle_gpus,
+    pattern_id,
+    reference_words,
+)
+
+# Pinned memory is a host resource on a node that runs pods: the default
+# stays modest.
+DEFAULT_BYTES = 256 << 20
+# What crosses the link in each pass of hostlink(), in order.
+PASS_PATHS = (
+    "kernel_write", "kernel_read", "copy_h2d", "copy_d2h",
+    "kernel_read", "host_write", "duplex", "kernel_read",
+)
+_SAMPLE_EDGE_BYTES = 4096  # CPU-checked head and tail of pass 0
+_SAMPLE_VECTORS = 64  # plus this many vectors at seeded random positions
+_HOST_WRITE_CHUNK_VECTORS = 1 << 16  # 1 MiB of pattern per numpy batch
+_COPY_WARMUP_BYTES = 1 << 20  # untimed first copy each way
+
+
+def _ext():
+    from .bandwidth import load_ext
+
+    return load_ext(required=True)
+
+
+def _device_index(device) -> int:
+    import torch
+
+    if device is None:
+        return int(torch.cuda.current_device())
+    if isinstance(device, int):
+        return device
+    d = torch.device(device)
+    return int(torch.cuda.current_device()) if d.index is None else int(d.index)
+
+
+def default_blocks():
+    """(DEFAULT_READ_BLOCKS, DEFAULT_WRITE_BLOCKS) of the built kernels:
+    the grid per direction when ``blocks`` is 0."""
+    ext = _ext()
+    return int(ext.HOSTLINK_DEFAULT_READ_BLOCKS), int(ext.HOSTLINK_DEFAULT_WRITE_BLOCKS)
+
+
+# -- thin wrappers -------------------------------------------------------------
+
+def alloc(nbytes: int, device=None):
+    """Pinned, mapped, fine-grained host memory as a CPU uint8 tensor
+    (``.numpy()`` views it); freed with the tensor."""
+    return _ext().hostlink_alloc(int(nbytes), _device_index(device))
+
+
+def fill_pattern(host, pattern: Pattern, seed: int = 0, device=None, blocks: int = 0) -> None:
+    """The GPU stores a pattern straight into a pinned CPU tensor
+    (contiguous, 16-byte aligned, nbytes a positive multiple of 16),
+    indexed from the tensor's own first byte.  Returns after the kernel
+    has finished.  A pageable tensor raises RuntimeError."""
+    _ext().hostlink_fill(host, pattern_id(pattern), int(seed), _device_index(device),
+                         int(blocks))
+
+
+def verify_pattern(host, pattern: Pattern, seed: int = 0, device=None,
+                   max_records: int = 16, blocks: int = 0) -> VerifyResult:
+    """The GPU loads a pinned CPU tensor and compares every word with
+    the pattern."""
+    return _to_result(_ext().hostlink_verify(
+        host, pattern_id(pattern), int(seed), _device_index(device), int(max_records),
+        int(blocks)))
+
+
+def duplex(read_host, read_pattern: Pattern, write_host, write_pattern: Pattern,
+           seed: int = 0, device=None, max_records: int = 16,
+           read_blocks: int = 0, write_blocks: int = 0) -> VerifyResult:
+    """One launch that verifies ``read_host`` while it fills
+    ``write_host``, so both directions of the link carry traffic at
+    once.  The two tensors must not overlap; each is indexed from its
+    own first byte.  Returns the verify result of the read side."""
+    return _to_result(_ext().hostlink_duplex(
+        read_host, pattern_id(read_pattern), write_host, pattern_id(write_pattern),
+        int(seed), _device_index(device), int(max_records), int(read_blocks),
+        int(write_blocks)))
+
+
+# -- PCIe link state -------------------------------------------------------------
+
+_SPEED_RE = re.compile(r"^\s*([0-9]+(?:\.[0-9]+)?)\s*GT/s")
+
+
+def read_pcie_link(bdf: str, sysfs_root: str = "/sys") -> Optional[dict]:
+    """Trained and maximum speed and width of a PCI device, and its NUMA
+    node, read from sysfs; None if anything is missing or unparsable.
+    ``downtrained`` says the link runs below its maximum speed or width.
+    Informative only."""
+    if not bdf:
+        return None
+    base = os.path.join(sysfs_root, "bus", "pci", "devices", bdf)
+
+    def read(name: str) -> str:
+        with open(os.path.join(base, name)) as f:
+            return f.read().strip()
+
+    def speed(name: str) -> float:
+        m = _SPEED_RE.match(read(name))  # "32.0 GT/s PCIe"
+        if m is None:
+            raise ValueError(name)
+        return float(m.group(1))
+
+    try:
+        out = {
+            "speed_gts": speed("current_link_speed"),
+            "max_speed_gts": speed("max_link_speed"),
+            "width": int(read("current_link_width")),
+            "max_width": int(read("max_link_width")),
+            "numa_node": int(read("numa_node")),
+        }
+    except (OSError, ValueError):
+        return None
+    if out["width"] <= 0 or out["max_width"] <= 0:
+        return None
+    out["downtrained"] = (out["speed_gts"] < out["max_speed_gts"]
+                          or out["width"] < out["max_width"])
+    return out
+
+
+def _device_bdf(index: int) -> str:
+    import torch
+
+    p = torch.cuda.get_device_properties(index)
+    return "%04x:%02x:%02x.0" % (p.pci_domain_id, p.pci_bus_id, p.pci_device_id)
+
+
+# -- the probe --------------------------------------------------------------------
+
+ONE_WAY_FIGURES = ("kernel_h2d_gbps", "kernel_d2h_gbps", "copy_h2d_gbps", "copy_d2h_gbps")
+
+
+def _below_floor(rec: dict, min_gbps: float) -> bool:
+    """A floor above 0 with any one-way figure of the result dict under
+    it; the duplex figure is not a one-way figure."""
+    return min_gbps > 0 and any(
+        rec.get(k) is not None and float(rec[k]) < min_gbps for k in ONE_WAY_FIGURES)
+
+
+@dataclass
+class HostlinkResult:
+    ok: bool = True
+    bytes_tested: int = 0
+    passes: int = 0
+    mismatched_words: int = 0  # found by the GPU, all passes
+    first_bad_offset: Optional[int] = None  # bytes from the buffer start
+    bad_bits_mask: int = 0
+    # {"pass", "path", "offset", "word_index", "expected", "got"} per logged word
+    records: List[Dict] = field(default_factory=list)
+    records_dropped: int = 0
+    cpu_sample_mismatches: int = 0  # found by the CPU in what the GPU wrote (pass 0)
+    elapsed_s: float = 0.0  # sum of the timed passes
+    kernel_h2d_gbps: float = 0.0  # GPU loads from host memory, best kernel_read pass
+    kernel_d2h_gbps: float = 0.0  # GPU stores to host memory
+    copy_h2d_gbps: float = 0.0  # the runtime's copy, host to device
+    copy_d2h_gbps: float = 0.0
+    duplex_gbps: float = 0.0  # read + written bytes over the one kernel's time
+    min_gbps: float = 0.0
+    below_floor: bool = False
+    link: Optional[dict] = None  # read_pcie_link() of the GPU
+
+    def apply_floor(self, min_gbps: float) -> None:
+        """Set min_gbps and below_floor.  Never touches ok."""
+        self.min_gbps = float(min_gbps)
+        self.below_floor = _below_floor(self.to_dict(), self.min_gbps)
+
+    def to_dict(self) -> dict:
+        return {
+            "ok": bool(self.ok),
+            "bytes_tested": int(self.bytes_tested),
+            "passes": int(self.passes),
+            "mismatched_words": int(self.mismatched_words),
+            "first_bad_offset": self.first_bad_offset,
+            "bad_bits_mask": int(self.bad_bits_mask),
+            "records": [dict(r) for r in self.records],
+            "records_dropped": int(self.records_dropped),
+            "cpu_sample_mismatches": int(self.cpu_sample_mismatches),
+            "elapsed_s": float(self.elapsed_s),
+            "kernel_h2d_gbps": float(self.kernel_h2d_gbps),
+            "kernel_d2h_gbps": float(self.kernel_d2h_gbps),
+            "copy_h2d_gbps": float(self.copy_h2d_gbps),
+            "copy_d2h_gbps": float(self.copy_d2h_gbps),
+            "duplex_gbps": float(self.duplex_gbps),
+            "min_gbps": float(self.min_gbps),
+            "below_floor": bool(self.below_floor),
+            "link": dict(self.link) if self.link is not None else None,
+        }
+
+
+def _sample_vectors(n_vectors: int, seed: int):
+    """Sorted vector indices the CPU checks after pass 0: the first and
+    the last 4 KiB and 64 seeded random positions."""
+    import numpy as np
+
+    edge = min(_SAMPLE_EDGE_BYTES // 16, n_vectors)
+    rng = np.random.default_rng(int(seed))
+    picks = rng.integers(0, n_vectors, size=_SAMPLE_VECTORS, dtype=np.int64)
+    return np.unique(np.concatenate([
+        np.arange(edge, dtype=np.int64),
+        np.arange(n_vectors - edge, n_vectors, dtype=np.int64),
+        picks,
+    ]))
+
+
+def _host_write(words, pattern: Pattern, seed: int) -> None:
+    """The CPU writes a pattern into a uint32 numpy view, in batches."""
+    n_vectors = len(words) // 4
+    for v0 in range(0, n_vectors, _HOST_WRITE_CHUNK_VECTORS):
+        n = min(_HOST_WRITE_CHUNK_VECTORS, n_vectors - v0)
+        words[4 * v0:4 * (v0 + n)] = reference_words(v0, n, pattern, seed)
+
+
+def hostlink(
+    nbytes: int = DEFAULT_BYTES,
+    seed: int = 0,
+    max_records: int = 16,
+    device=None,
+    min_gbps: float = 0.0,
+    _after_pass: Optional[Callable] = None,
+) -> HostlinkResult:
+    """Allocate one pinned host buffer H and one device buffer D of
+    ``nbytes`` and run eight passes (``PASS_PATHS``):
+
+      0 kernel_write  the GPU stores addr into H; the CPU checks a sample
+      1 kernel_read   the GPU loads H and verifies addr
+      2 copy_h2d      D.copy_(H), then memcheck verifies D == addr
+      3 copy_d2h      memcheck fills D with addr_inv, then H.copy_(D)
+      4 kernel_read   the GPU verifies H == addr_inv
+      5 host_write    the CPU writes checker into H, the GPU verifies it
+      6 duplex        one kernel verifies the lower half of H (checker)
+                      while it fills the upper half with walk1
+      7 kernel_read   the GPU verifies the upper half == walk1
+
+    Only the transfer named by a pass is timed (perf_counter around a
+    synchronised pass); the checks and fills on D and the CPU's own work
+    are not.  Data the CPU wrote and only the GPU read (pass 5), and
+    data the GPU wrote and the CPU read (the pass 0 sample), cannot be
+    faked by a cache on the GPU side.
+
+    ``ok`` is about data alone.  ``below_floor`` says a one-way figure
+    was under ``min_gbps`` (0 = no floor) and never changes ``ok``.
+    Records are capped at ``max_records`` per pass and overall; offsets
+    are bytes from the start of H.
+
+    ``_after_pass(pass_index, host_numpy_view)`` is a test hook called
+    after every pass with the uint8 numpy view of H, so that a test can
+    corrupt host memory between passes; the CPU's sample of pass 0 is
+    taken after the hook.
+    """
+    import numpy as np
+    import torch
+
+    nbytes = int(nbytes)
+    if nbytes <= 0 or nbytes % 32:
+        raise ValueError(f"hostlink: nbytes must be a positive multiple of 32, got {nbytes}")
+    seed = int(seed)
+    max_records = int(max_records)
+    ext = _ext()
+    index = _device_index(device)
+    dev = torch.device("cuda", index)
+    H = ext.hostlink_alloc(nbytes, index)
+    D = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    # The runtime sets its copy path up on a process's first copy each
+    # way, and this probe is a process's whole life: warm both before
+    # anything is timed, while neither buffer holds data yet.
+    warm = min(nbytes, _COPY_WARMUP_BYTES)
+    D[:warm].copy_(H[:warm], non_blocking=True)
+    H[:warm].copy_(D[:warm])
+    torch.cuda.synchronize(dev)
+    view = H.numpy()
+    half = nbytes // 2
+    lower, upper = H[:half], H[half:]
+
+    res = HostlinkResult(bytes_tested=nbytes)
+    try:
+        res.link = read_pcie_link(_device_bdf(index))
+    except Exception:  # informative only
+        res.link = None
+    read_gbps: List[float] = []
+
+    def timed(fn):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+        res.elapsed_s += dt
+        return out, dt
+
+    def gbps(moved: int, dt: float) -> float:
+        return moved / dt / 1e9 if dt > 0 else 0.0
+
+    def record(idx: int, word: int, expected: int, got: int, base: int) -> None:
+        if len(res.records) < max_records:
+            res.records.append({
+                "pass": idx, "path": PASS_PATHS[idx], "offset": base + word * 4,
+                "word_index": (base + word * 4) // 4, "expected": expected, "got": got,
+            })
+
+    def first_bad(offset: int) -> None:
+        if res.first_bad_offset is None or offset < res.first_bad_offset:
+            res.first_bad_offset = offset
+
+    def account(idx: int, vr: VerifyResult, base: int = 0) -> None:
+        if not vr.mismatched_words:
+            return
+        res.mismatched_words += vr.mismatched_words
+        res.bad_bits_mask |= vr.bad_bits_mask
+        first_bad(base + vr.first_bad_offset)
+        for word, expected, got in vr.records:
+            record(idx, word, expected, got, base)
+
+    def done(idx: int) -> None:
+        res.passes += 1
+        if _after_pass is not None:
+            _after_pass(idx, view)
+            torch.cuda.synchronize(dev)
+
+    def kernel_read(idx: int, host, pattern: str, base: int = 0) -> None:
+        raw, dt = timed(lambda: ext.hostlink_verify(
+            host, pattern_id(pattern), seed, index, max_records, 0))
+        read_gbps.append(gbps(host.nbytes, dt))
+        account(idx, _to_result(raw), base)
+        done(idx)
+
+    # 0: GPU -> host stores, checked by the CPU
+    _, dt = timed(lambda: ext.hostlink_fill(H, pattern_id("addr"), seed, index, 0))
+    res.kernel_d2h_gbps = gbps(nbytes, dt)
+    done(0)
+    words = view.view(np.uint32)
+    sample = _sample_vectors(nbytes // 16, seed)
+    for run in np.split(sample, np.nonzero(np.diff(sample) != 1)[0] + 1):
+        v0 = int(run[0])  # a run of consecutive vectors
+        want = reference_words(v0, len(run), "addr", seed)
+        got = words[4 * v0:4 * (v0 + len(run))]
+        for j in np.nonzero(got != want)[0]:
+            w = 4 * v0 + int(j)
+            res.cpu_sample_mismatches += 1
+            res.bad_bits_mask |= int(got[j]) ^ int(want[j])
+            first_bad(4 * w)
+            record(0, w, int(want[j]), int(got[j]), 0)
+    # 1: host -> GPU loads
+    kernel_read(1, H, "addr")
+    # 2: the runtime's copy, host -> device; D is checked in HBM
+    _, dt = timed(lambda: D.copy_(H, non_blocking=True))
+    res.copy_h2d_gbps = gbps(nbytes, dt)
+    account(2, _to_result(ext.verify_pattern(D, pattern_id("addr"), seed, max_records, 0)))
+    done(2)
+    # 3: the runtime's copy, device -> host; pass 4 checks it
+    ext.fill_pattern(D, pattern_id("addr_inv"), seed, 0)
+    _, dt = timed(lambda: H.copy_(D))
+    res.copy_d2h_gbps = gbps(nbytes, dt)
+    done(3)
+    kernel_read(4, H, "addr_inv")
+    # 5: CPU-authored data, read by the GPU alone
+    _host_write(words, "checker", seed)
+    account(5, _to_result(ext.hostlink_verify(
+        H, pattern_id("checker"), seed, index, max_records, 0)))
+    done(5)
+    # 6: both directions in one kernel
+    raw, dt = timed(lambda: ext.hostlink_duplex(
+        lower, pattern_id("checker"), upper, pattern_id("walk1"), seed, index,
+        max_records, 0, 0))
+    res.duplex_gbps = gbps(nbytes, dt)
+    account(6, _to_result(raw))
+    done(6)
+    kernel_read(7, upper, "walk1", base=half)
+
+    res.kernel_h2d_gbps = max(read_gbps)
+    res.ok = res.mismatched_words == 0 and res.cpu_sample_mismatches == 0
+    res.records_dropped = (res.mismatched_words + res.cpu_sample_mismatches
+                           - len(res.records))
+    res.apply_floor(min_gbps)
+    return res
+
+
+# -- child process -----------------------------------------------------------
+
+def run_hostlink_subprocess(index: int, nbytes: int = DEFAULT_BYTES,
+                            timeout_s: float = 120.0) -> dict:
+    """Run the hostlink CLI for GPU ``index`` in a fresh child process
+    (never exec: the parent may hold the GPU open) and return its JSON
+    record with ``exit_code`` added.  Serialised on memcheck's child
+    lock, so the three active probes never overlap.  Raises
+    subprocess.TimeoutExpired when the child overruns (it is killed
+    first)."""
+    cmd = [sys.executable, "-m", "kubegpu_amd.probe.hostlink",
+           "--device", str(int(index)), "--bytes", str(int(nbytes))]
+    env = dict(os.environ)
+    env["PYTHONPATH"] = _REPO_ROOT + os.pathsep + env["PYTHONPATH"] \
+        if env.get("PYTHONPATH") else _REPO_ROOT
+    with _child_lock:
+        out = subprocess.run(cmd, capture_output=True, timeout=timeout_s,
+                             env=env, text=True)
+    lines = out.stdout.strip().splitlines()
+    try:
+        rec = json.loads(lines[-1])
+    except (IndexError, ValueError):
+        rec = {"error": f"no JSON from hostlink child: {out.stderr[-500:]}"}
+        out.returncode = EXIT_CANNOT_RUN
+    rec["exit_code"] = out.returncode
+    return rec
+
+
+def hostlink_round(manager, runner: Callable[[int, int], dict], metrics=None,
+                   nbytes: int = DEFAULT_BYTES,
+                   max_process_count: Optional[int] = 0,
+                   min_gbps: float = 0.0) -> Dict[str, dict]:
+    """Check every idle GPU once and record the verdicts.
+
+    Same selection as ``memcheck_round`` (no allocation, process_count
+    at most ``max_process_count``, None ignores it), in index order;
+    ``runner(index, nbytes)`` is called, the GPU's PCIe link state
+    (``read_pcie_link`` of its bdf, read here in the parent) is attached
+    as ``link`` and ``min_gbps`` is applied, and the result dict is
+    recorded on the manager.  A figure below the floor is logged and
+    exported and leaves health alone.  A runner that raises, times out
+    or reports exit code 2 says nothing about the link: it is logged
+    and counted as an error, and the GPU's health is left as it was.
+    Returns {uuid: result}."""
+    from ..api import utils
+
+    out: Dict[str, dict] = {}
+    for index, uuid in idle_gpus(manager, max_process_count):
+        try:
+            rec = runner(index, nbytes)
+            if not isinstance(rec, dict):
+                raise TypeError(f"hostlink runner returned {type(rec).__name__}")
+            if rec.get("exit_code") == EXIT_CANNOT_RUN or "mismatched_words" not in rec:
+                raise RuntimeError(rec.get("error") or "hostlink could not run")
+        except Exception as e:  # not a link fault: health unchanged
+            utils.errorf("hostlink on GPU %s (index %d) did not run: %s", uuid, index, e)
+            if metrics is not None:
+                metrics.inc_hostlink_error(uuid)
+            out[uuid] = {"error": str(e), "exit_code": EXIT_CANNOT_RUN}
+            continue
+        gpu = manager.gpu_or_tombstone(uuid)
+        rec["link"] = read_pcie_link(gpu.bdf) if gpu is not None else None
+        rec["min_gbps"] = float(min_gbps)
+        rec["below_floor"] = _below_floor(rec, float(min_gbps))
+        if rec["below_floor"]:
+            utils.errorf(
+                "hostlink on GPU %s: below the %.1f GB/s floor (kernel h2d %.1f, "
+                "kernel d2h %.1f, copy h2d %.1f, copy d2h %.1f GB/s, link %s) — "
+                "health unchanged",
+                uuid, float(min_gbps), float(rec.get("kernel_h2d_gbps", 0.0)),
+                float(rec.get("kernel_d2h_gbps", 0.0)),
+                float(rec.get("copy_h2d_gbps", 0.0)),
+                float(rec.get("copy_d2h_gbps", 0.0)), rec["link"],
+            )
+        try:
+            manager.record_hostlink(uuid, rec)
+        except KeyError:  # vanished mid-round
+            continue
+        if metrics is not None:
+            metrics.set_gpu_hostlink(
+                uuid,
+                int(rec["mismatched_words"]) + int(rec.get("cpu_sample_mismatches", 0)),
+                float(rec.get("kernel_h2d_gbps", 0.0)),
+                float(rec.get("kernel_d2h_gbps", 0.0)),
+                bool(rec["below_floor"]), time.time(),
+            )
+        out[uuid] = rec
+    return out
+
+
+def main(argv=None) -> int:
+    import argparse
+
+    ap = argparse.ArgumentParser(prog="kubegpu-amd-hostlink")
+    ap.add_argument("--device", type=int, required=True, metavar="INDEX")
+    ap.add_argument("--bytes", type=int, default=DEFAULT_BYTES, metavar="N")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--min-gbps", type=float, default=0.0, metavar="X")
+    args = ap.parse_args(argv)
+
+    # pin before torch / HIP initialise (same as memcheck)
+    os.environ["ROCR_VISIBLE_DEVICES"] = str(args.device)
+    rec: dict
+    try:
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("no GPU visible")
+        torch.cuda.set_device(0)
+        result = hostlink(nbytes=args.bytes, seed=args.seed, min_gbps=args.min_gbps)
+        rec = result.to_dict()
+        code = EXIT_PASS if result.ok else EXIT_MISMATCH
+    except Exception as e:  # no GPU, extension missing, pinned allocation failed, bad size
+        rec = {"error": f"{type(e).__name__}: {e}"}
+        code = EXIT_CANNOT_RUN
+    rec["device"] = args.device
+    print(json.dumps(rec), flush=True)
+    return code
+
+
+if __name__ == "__main__":
+    sys.exit(main())

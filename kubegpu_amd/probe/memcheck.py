@@ -289,7 +289,7 @@ def memcheck(
 # -- child process -----------------------------------------------------------
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-_child_lock = threading.Lock()  # one active-probe child at a time (cucheck too)
+_child_lock = threading.Lock()  # one active-probe child at a time (cucheck, hostlink too)
 
 
 def run_memcheck_subprocess(index: int, nbytes: int = DEFAULT_BYTES,
@@ -320,7 +320,8 @@ def idle_gpus(manager, max_process_count: Optional[int]) -> List[Tuple[int, str]
     """(index, uuid) of every present GPU an active probe may take, in
     index order: no allocation, and process_count at most
     max_process_count (None ignores process_count).  Shared with the
-    compute-unit probe (probe/cucheck.py)."""
+    compute-unit probe (probe/cucheck.py) and the host-link probe
+    (probe/hostlink.py)."""
     with manager._lock:
         return sorted(
             (g.index, u) for u, g in manager.gpus.items()

@@ -77,6 +77,22 @@ def main(argv=None) -> int:
     ap.add_argument("--cucheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the compute-unit integrity probe")
+    ap.add_argument("--hostlink-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the host-link integrity probe over the idle "
+                         "GPUs every SECONDS from the health loop; a GPU "
+                         "with words that crossed the link wrong turns "
+                         "Unhealthy (0 = off)")
+    ap.add_argument("--hostlink-bytes", type=int, default=256 << 20,
+                    help="pinned host buffer (and device buffer) size per "
+                         "GPU for the host-link integrity probe")
+    ap.add_argument("--hostlink-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the host-link integrity probe")
+    ap.add_argument("--hostlink-min-gbps", type=float, default=0.0,
+                    help="report (log, metric) a GPU whose one-way host-link "
+                         "bandwidth is under this many GB/s; never changes "
+                         "health (0 = no floor)")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -132,6 +148,7 @@ def main(argv=None) -> int:
     watcher_started = False
     next_memcheck = time.monotonic()  # first round on the first tick
     next_cucheck = time.monotonic()
+    next_hostlink = time.monotonic()
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -209,6 +226,19 @@ def main(argv=None) -> int:
                               max_process_count=args.cucheck_max_procs)
             except Exception as e:  # never let the probe kill the agent
                 utils.errorf("agent: cucheck round failed: %s", e)
+            plugin.servicer.notify()
+        # active host-link integrity probe, same shape and the same lock
+        if args.hostlink_interval > 0 and time.monotonic() >= next_hostlink:
+            next_hostlink = time.monotonic() + args.hostlink_interval
+            try:
+                from ..probe.hostlink import hostlink_round, run_hostlink_subprocess
+
+                hostlink_round(manager, run_hostlink_subprocess, METRICS,
+                               args.hostlink_bytes,
+                               max_process_count=args.hostlink_max_procs,
+                               min_gbps=args.hostlink_min_gbps)
+            except Exception as e:  # never let the probe kill the agent
+                utils.errorf("agent: hostlink round failed: %s", e)
             plugin.servicer.notify()
         for uuid, ok in manager.device_health().items():
             g = manager.gpu_or_tombstone(uuid)
