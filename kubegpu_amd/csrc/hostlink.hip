@@ -47,20 +47,23 @@
 
 // Grid-stride bodies over one role's own buffer with its own block
 // count: `block` of `nblocks` (the launch's for the single-role
-// kernels, the role's share of it for the duplex kernel).
+// kernels, the role's share of it for the duplex kernel).  `first` is
+// the pattern's vector index of the buffer's first vector: the pattern
+// is generated for first + i, the buffer is addressed with i, and every
+// reported word index stays relative to the buffer start.
 template <int FAMILY>
-__device__ __forceinline__ void fill_host(uint4v* __restrict__ dst, size_t n4,
+__device__ __forceinline__ void fill_host(uint4v* __restrict__ dst, size_t n4, u64 first,
                                           unsigned int seed, unsigned int inv,
                                           size_t block, size_t nblocks) {
   size_t i = block * BLOCK + threadIdx.x;
   size_t stride = nblocks * BLOCK;
   for (; i < n4; i += stride)
-    __builtin_nontemporal_store(pattern_vec<FAMILY>(i, seed, inv), &dst[i]);
+    __builtin_nontemporal_store(pattern_vec<FAMILY>(first + i, seed, inv), &dst[i]);
 }
 
 template <int FAMILY>
 __device__ __forceinline__ void verify_host(const uint4v* __restrict__ src, size_t n4,
-                                            unsigned int seed, unsigned int inv,
+                                            u64 first, unsigned int seed, unsigned int inv,
                                             size_t block, size_t nblocks,
                                             u64* __restrict__ res, int max_records) {
   size_t i = block * BLOCK + threadIdx.x;
@@ -68,22 +71,22 @@ __device__ __forceinline__ void verify_host(const uint4v* __restrict__ src, size
   Tally t = {0, ~0ULL, 0};
   for (; i < n4; i += stride) {
     uint4v got = __builtin_nontemporal_load(&src[i]);
-    check_vec(t, got, pattern_vec<FAMILY>(i, seed, inv), i, res, max_records);
+    check_vec(t, got, pattern_vec<FAMILY>(first + i, seed, inv), i, res, max_records);
   }
   reduce_tally(t, res);
 }
 
 template <int FAMILY>
-__global__ void hostlink_fill_kernel(uint4v* __restrict__ dst, size_t n4,
+__global__ void hostlink_fill_kernel(uint4v* __restrict__ dst, size_t n4, u64 first,
                                      unsigned int seed, unsigned int inv) {
-  fill_host<FAMILY>(dst, n4, seed, inv, blockIdx.x, gridDim.x);
+  fill_host<FAMILY>(dst, n4, first, seed, inv, blockIdx.x, gridDim.x);
 }
 
 template <int FAMILY>
 __global__ void hostlink_verify_kernel(const uint4v* __restrict__ src, size_t n4,
-                                       unsigned int seed, unsigned int inv,
+                                       u64 first, unsigned int seed, unsigned int inv,
                                        u64* __restrict__ res, int max_records) {
-  verify_host<FAMILY>(src, n4, seed, inv, blockIdx.x, gridDim.x, res, max_records);
+  verify_host<FAMILY>(src, n4, first, seed, inv, blockIdx.x, gridDim.x, res, max_records);
 }
 
 // One launch, two roles.  The role depends on blockIdx.x alone, so it is
@@ -93,17 +96,18 @@ __global__ void hostlink_verify_kernel(const uint4v* __restrict__ src, size_t n4
 // it; the writer path holds no barrier and touches neither LDS nor res.
 template <int READ_FAMILY, int WRITE_FAMILY>
 __global__ void hostlink_duplex_kernel(const uint4v* __restrict__ src, size_t read_n4,
-                                       unsigned int read_inv,
+                                       u64 read_first, unsigned int read_inv,
                                        uint4v* __restrict__ dst, size_t write_n4,
-                                       unsigned int write_inv, unsigned int seed,
+                                       u64 write_first, unsigned int write_inv,
+                                       unsigned int seed,
                                        unsigned int read_blocks,
                                        u64* __restrict__ res, int max_records) {
   if (blockIdx.x < read_blocks) {
-    verify_host<READ_FAMILY>(src, read_n4, seed, read_inv, blockIdx.x, read_blocks,
-                             res, max_records);
+    verify_host<READ_FAMILY>(src, read_n4, read_first, seed, read_inv, blockIdx.x,
+                             read_blocks, res, max_records);
   } else {
-    fill_host<WRITE_FAMILY>(dst, write_n4, seed, write_inv, blockIdx.x - read_blocks,
-                            gridDim.x - read_blocks);
+    fill_host<WRITE_FAMILY>(dst, write_n4, write_first, seed, write_inv,
+                            blockIdx.x - read_blocks, gridDim.x - read_blocks);
   }
 }
 
@@ -160,6 +164,16 @@ static unsigned int check_seed(int64_t seed) {
   return (unsigned int)seed;
 }
 
+// first_vector -> the kernels' u64 base.  The binding is int64, and
+// first_vector + n4 must not wrap: at most 2^63.
+static u64 check_first(int64_t first_vector, size_t n4, const char* what) {
+  TORCH_CHECK(first_vector >= 0, "hostlink: ", what, " must not be negative, got ",
+              first_vector);
+  TORCH_CHECK((u64)first_vector + (u64)n4 <= (1ULL << 63), "hostlink: ", what, " ",
+              first_vector, " + ", n4, " vectors exceeds 2^63");
+  return (u64)first_vector;
+}
+
 static void check_blocks(int64_t blocks_arg) {
   TORCH_CHECK(blocks_arg >= 0 && blocks_arg <= MAX_BLOCKS,
               "hostlink: blocks must be in 0..", MAX_BLOCKS, ", got ", blocks_arg);
@@ -211,7 +225,7 @@ at::Tensor hostlink_alloc(int64_t nbytes, int64_t device_arg) {
 // next, and a pinned tensor released while the kernel still wrote to it
 // could be handed to someone else.
 void hostlink_fill(at::Tensor host, int64_t pattern, int64_t seed_arg,
-                   int64_t device_arg, int64_t blocks_arg) {
+                   int64_t device_arg, int64_t blocks_arg, int64_t first_vector) {
   check_pattern(pattern);
   unsigned int seed = check_seed(seed_arg);
   check_blocks(blocks_arg);
@@ -220,21 +234,22 @@ void hostlink_fill(at::Tensor host, int64_t pattern, int64_t seed_arg,
       at::Device(at::kCUDA, (c10::DeviceIndex)device));
   uint4v* p = check_host(host, "host");
   size_t n4 = host.nbytes() / 16;
+  u64 first = check_first(first_vector, n4, "first_vector");
   unsigned int blocks = pick_blocks(blocks_arg, n4, DEFAULT_WRITE_BLOCKS);
   unsigned int inv = inv_of(pattern);
   hipStream_t stream = at::hip::getCurrentHIPStream((c10::DeviceIndex)device);
   switch (pattern >> 1) {
     case 0:
       hipLaunchKernelGGL(hostlink_fill_kernel<0>, dim3(blocks), dim3(BLOCK), 0, stream,
-                         p, n4, seed, inv);
+                         p, n4, first, seed, inv);
       break;
     case 1:
       hipLaunchKernelGGL(hostlink_fill_kernel<1>, dim3(blocks), dim3(BLOCK), 0, stream,
-                         p, n4, seed, inv);
+                         p, n4, first, seed, inv);
       break;
     default:
       hipLaunchKernelGGL(hostlink_fill_kernel<2>, dim3(blocks), dim3(BLOCK), 0, stream,
-                         p, n4, seed, inv);
+                         p, n4, first, seed, inv);
       break;
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
@@ -243,7 +258,7 @@ void hostlink_fill(at::Tensor host, int64_t pattern, int64_t seed_arg,
 
 VerifyOut hostlink_verify(at::Tensor host, int64_t pattern, int64_t seed_arg,
                           int64_t device_arg, int64_t max_records,
-                          int64_t blocks_arg) {
+                          int64_t blocks_arg, int64_t first_vector) {
   check_pattern(pattern);
   unsigned int seed = check_seed(seed_arg);
   check_blocks(blocks_arg);
@@ -253,6 +268,7 @@ VerifyOut hostlink_verify(at::Tensor host, int64_t pattern, int64_t seed_arg,
       at::Device(at::kCUDA, (c10::DeviceIndex)device));
   const uint4v* p = check_host(host, "host");
   size_t n4 = host.nbytes() / 16;
+  u64 first = check_first(first_vector, n4, "first_vector");
   unsigned int blocks = pick_blocks(blocks_arg, n4, DEFAULT_READ_BLOCKS);
   unsigned int inv = inv_of(pattern);
   at::Tensor res = make_result(device, max_records);
@@ -262,15 +278,15 @@ VerifyOut hostlink_verify(at::Tensor host, int64_t pattern, int64_t seed_arg,
   switch (pattern >> 1) {
     case 0:
       hipLaunchKernelGGL(hostlink_verify_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv, r, mr);
+                         stream, p, n4, first, seed, inv, r, mr);
       break;
     case 1:
       hipLaunchKernelGGL(hostlink_verify_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv, r, mr);
+                         stream, p, n4, first, seed, inv, r, mr);
       break;
     default:
       hipLaunchKernelGGL(hostlink_verify_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv, r, mr);
+                         stream, p, n4, first, seed, inv, r, mr);
       break;
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
@@ -279,8 +295,8 @@ VerifyOut hostlink_verify(at::Tensor host, int64_t pattern, int64_t seed_arg,
 
 #define DUPLEX_LAUNCH(R, W)                                                     \
   hipLaunchKernelGGL((hostlink_duplex_kernel<R, W>), dim3(rblocks + wblocks),   \
-                     dim3(BLOCK), 0, stream, rp, rn4, rinv, wp, wn4, winv, seed, \
-                     rblocks, r, mr)
+                     dim3(BLOCK), 0, stream, rp, rn4, rfirst, rinv, wp, wn4, wfirst, \
+                     winv, seed, rblocks, r, mr)
 #define DUPLEX_WRITE(R)                 \
   switch (write_pattern >> 1) {         \
     case 0: DUPLEX_LAUNCH(R, 0); break; \
@@ -291,7 +307,8 @@ VerifyOut hostlink_verify(at::Tensor host, int64_t pattern, int64_t seed_arg,
 VerifyOut hostlink_duplex(at::Tensor read_host, int64_t read_pattern,
                           at::Tensor write_host, int64_t write_pattern,
                           int64_t seed_arg, int64_t device_arg, int64_t max_records,
-                          int64_t read_blocks_arg, int64_t write_blocks_arg) {
+                          int64_t read_blocks_arg, int64_t write_blocks_arg,
+                          int64_t read_first_vector, int64_t write_first_vector) {
   check_pattern(read_pattern);
   check_pattern(write_pattern);
   unsigned int seed = check_seed(seed_arg);
@@ -307,6 +324,8 @@ VerifyOut hostlink_duplex(at::Tensor read_host, int64_t read_pattern,
   TORCH_CHECK(ra + read_host.nbytes() <= wa || wa + write_host.nbytes() <= ra,
               "hostlink: read_host and write_host overlap");
   size_t rn4 = read_host.nbytes() / 16, wn4 = write_host.nbytes() / 16;
+  u64 rfirst = check_first(read_first_vector, rn4, "read_first_vector");
+  u64 wfirst = check_first(write_first_vector, wn4, "write_first_vector");
   unsigned int rblocks = pick_blocks(read_blocks_arg, rn4, DEFAULT_READ_BLOCKS);
   unsigned int wblocks = pick_blocks(write_blocks_arg, wn4, DEFAULT_WRITE_BLOCKS);
   unsigned int rinv = inv_of(read_pattern), winv = inv_of(write_pattern);
@@ -340,13 +359,14 @@ void bind_hostlink(py::module_& m) {
         "the GPU stores a memcheck pattern into pinned host memory",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("host"), py::arg("pattern"), py::arg("seed"), py::arg("device"),
-        py::arg("blocks") = 0);
+        py::arg("blocks") = 0, py::arg("first_vector") = 0);
   m.def("hostlink_verify", &hostlink_verify,
         "the GPU loads pinned host memory and verifies a pattern -> "
         "(mismatched_words, first_bad_word, bad_bits_mask, records)",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("host"), py::arg("pattern"), py::arg("seed"), py::arg("device"),
-        py::arg("max_records") = 16, py::arg("blocks") = 0);
+        py::arg("max_records") = 16, py::arg("blocks") = 0,
+        py::arg("first_vector") = 0);
   m.def("hostlink_duplex", &hostlink_duplex,
         "one launch verifying read_host while filling write_host -> the "
         "verify tuple of the read side",
@@ -354,5 +374,6 @@ void bind_hostlink(py::module_& m) {
         py::arg("read_host"), py::arg("read_pattern"), py::arg("write_host"),
         py::arg("write_pattern"), py::arg("seed"), py::arg("device"),
         py::arg("max_records") = 16, py::arg("read_blocks") = 0,
-        py::arg("write_blocks") = 0);
+        py::arg("write_blocks") = 0, py::arg("read_first_vector") = 0,
+        py::arg("write_first_vector") = 0);
 }

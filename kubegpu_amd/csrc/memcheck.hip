@@ -35,43 +35,57 @@
 // and 3,348 at 512; 1536 = 6 wg per CU sits in its middle.
 #define VERIFY_BLOCKS 1536
 
+// `first` is the pattern's vector index of the buffer's first vector
+// (first_vector).  The loops run over the pattern index v = first + i
+// and address the buffer with i = v - first, so every reported word
+// index stays relative to the buffer start; first + n4 cannot wrap, the
+// host keeps it within 2^63.  Written this way the hot loops keep the
+// instruction count they had when v was i: looping over i and adding
+// first inside cost the addr fill three more VALU instructions per
+// vector and 1.5 % of its bandwidth at 1 GiB
+// (profiles/memcheck_first_vector_ab_mi355x.json), and the verify
+// loops step their pointer so that i is only needed on a mismatch.
 template <int FAMILY>
-__global__ void fill_pattern_kernel(uint4v* __restrict__ dst, size_t n4,
+__global__ void fill_pattern_kernel(uint4v* __restrict__ dst, size_t n4, u64 first,
                                     unsigned int seed, unsigned int inv) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u64 v = first + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u64 end = first + n4;
   size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < n4; i += stride)
-    __builtin_nontemporal_store(pattern_vec<FAMILY>(i, seed, inv), &dst[i]);
+  for (; v < end; v += stride)
+    __builtin_nontemporal_store(pattern_vec<FAMILY>(v, seed, inv), &dst[v - first]);
 }
 
 template <int FAMILY>
 __global__ void verify_pattern_kernel(const uint4v* __restrict__ src, size_t n4,
-                                      unsigned int seed, unsigned int inv,
+                                      u64 first, unsigned int seed, unsigned int inv,
                                       u64* __restrict__ res, int max_records) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u64 v = first + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u64 end = first + n4;
   size_t stride = (size_t)gridDim.x * blockDim.x;
   Tally t = {0, ~0ULL, 0};
-  for (; i < n4; i += stride) {
-    uint4v got = __builtin_nontemporal_load(&src[i]);
-    check_vec(t, got, pattern_vec<FAMILY>(i, seed, inv), i, res, max_records);
+  for (src += v - first; v < end; v += stride, src += stride) {
+    uint4v got = __builtin_nontemporal_load(src);
+    check_vec(t, got, pattern_vec<FAMILY>(v, seed, inv), v - first, res, max_records);
   }
   reduce_tally(t, res);
 }
 
 // Fused read-check-write pass (the moving-inversions step): every word
-// ends up holding the next pattern whether or not it matched.
+// ends up holding the next pattern whether or not it matched.  Both
+// patterns count from the same `first`.
 template <int EXPECT_FAMILY, int NEXT_FAMILY>
-__global__ void verify_then_fill_kernel(uint4v* __restrict__ buf, size_t n4,
+__global__ void verify_then_fill_kernel(uint4v* __restrict__ buf, size_t n4, u64 first,
                                         unsigned int seed, unsigned int expect_inv,
                                         unsigned int next_inv,
                                         u64* __restrict__ res, int max_records) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u64 v = first + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  u64 end = first + n4;
   size_t stride = (size_t)gridDim.x * blockDim.x;
   Tally t = {0, ~0ULL, 0};
-  for (; i < n4; i += stride) {
-    uint4v got = __builtin_nontemporal_load(&buf[i]);
-    __builtin_nontemporal_store(pattern_vec<NEXT_FAMILY>(i, seed, next_inv), &buf[i]);
-    check_vec(t, got, pattern_vec<EXPECT_FAMILY>(i, seed, expect_inv), i, res,
+  for (buf += v - first; v < end; v += stride, buf += stride) {
+    uint4v got = __builtin_nontemporal_load(buf);
+    __builtin_nontemporal_store(pattern_vec<NEXT_FAMILY>(v, seed, next_inv), buf);
+    check_vec(t, got, pattern_vec<EXPECT_FAMILY>(v, seed, expect_inv), v - first, res,
               max_records);
   }
   reduce_tally(t, res);
@@ -104,6 +118,16 @@ static unsigned int check_seed(int64_t seed) {
   return (unsigned int)seed;
 }
 
+// first_vector -> the kernels' u64 base.  The binding is int64, and
+// first_vector + n4 must not wrap: at most 2^63.
+static u64 check_first(int64_t first_vector, size_t n4) {
+  TORCH_CHECK(first_vector >= 0, "memcheck: first_vector must not be negative, got ",
+              first_vector);
+  TORCH_CHECK((u64)first_vector + (u64)n4 <= (1ULL << 63), "memcheck: first_vector ",
+              first_vector, " + ", n4, " vectors exceeds 2^63");
+  return (u64)first_vector;
+}
+
 static at::Tensor make_result(const at::Tensor& buf, int64_t max_records) {
   TORCH_CHECK(max_records >= 0 && max_records <= MAX_RECORDS_LIMIT,
               "memcheck: max_records must be in 0..", MAX_RECORDS_LIMIT);
@@ -114,9 +138,10 @@ static at::Tensor make_result(const at::Tensor& buf, int64_t max_records) {
 }
 
 void fill_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
-                  int64_t blocks_arg) {
+                  int64_t blocks_arg, int64_t first_vector) {
   size_t n4 = check_buf(buf, pattern);
   unsigned int seed = check_seed(seed_arg);
+  u64 first = check_first(first_vector, n4);
   int blocks = pick_blocks(blocks_arg, n4, DEFAULT_WRITE_BLOCKS);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
   auto stream = at::hip::getCurrentHIPStream();
@@ -125,24 +150,26 @@ void fill_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
   switch (pattern >> 1) {
     case 0:
       hipLaunchKernelGGL(fill_pattern_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv);
+                         stream, p, n4, first, seed, inv);
       break;
     case 1:
       hipLaunchKernelGGL(fill_pattern_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv);
+                         stream, p, n4, first, seed, inv);
       break;
     default:
       hipLaunchKernelGGL(fill_pattern_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv);
+                         stream, p, n4, first, seed, inv);
       break;
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 VerifyOut verify_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
-                         int64_t max_records, int64_t blocks_arg) {
+                         int64_t max_records, int64_t blocks_arg,
+                         int64_t first_vector) {
   size_t n4 = check_buf(buf, pattern);
   unsigned int seed = check_seed(seed_arg);
+  u64 first = check_first(first_vector, n4);
   int blocks = pick_blocks(blocks_arg, n4, VERIFY_BLOCKS);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
   at::Tensor res = make_result(buf, max_records);
@@ -154,15 +181,15 @@ VerifyOut verify_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
   switch (pattern >> 1) {
     case 0:
       hipLaunchKernelGGL(verify_pattern_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv, r, mr);
+                         stream, p, n4, first, seed, inv, r, mr);
       break;
     case 1:
       hipLaunchKernelGGL(verify_pattern_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv, r, mr);
+                         stream, p, n4, first, seed, inv, r, mr);
       break;
     default:
       hipLaunchKernelGGL(verify_pattern_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, seed, inv, r, mr);
+                         stream, p, n4, first, seed, inv, r, mr);
       break;
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
@@ -171,7 +198,7 @@ VerifyOut verify_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
 
 #define VTF_LAUNCH(E, N)                                                       \
   hipLaunchKernelGGL((verify_then_fill_kernel<E, N>), dim3(blocks), dim3(BLOCK), \
-                     0, stream, p, n4, seed, einv, ninv, r, mr)
+                     0, stream, p, n4, first, seed, einv, ninv, r, mr)
 #define VTF_NEXT(E)                 \
   switch (next_pattern >> 1) {      \
     case 0: VTF_LAUNCH(E, 0); break; \
@@ -181,12 +208,14 @@ VerifyOut verify_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
 
 VerifyOut verify_then_fill(at::Tensor buf, int64_t expect_pattern,
                            int64_t next_pattern, int64_t seed_arg,
-                           int64_t max_records, int64_t blocks_arg) {
+                           int64_t max_records, int64_t blocks_arg,
+                           int64_t first_vector) {
   size_t n4 = check_buf(buf, expect_pattern);
   TORCH_CHECK(next_pattern >= 0 && next_pattern < N_PATTERNS,
               "memcheck: pattern id ", next_pattern, " out of range 0..",
               N_PATTERNS - 1);
   unsigned int seed = check_seed(seed_arg);
+  u64 first = check_first(first_vector, n4);
   int blocks = pick_blocks(blocks_arg, n4, DEFAULT_COPY_BLOCKS);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
   at::Tensor res = make_result(buf, max_records);
@@ -215,16 +244,18 @@ void bind_memcheck(py::module_& m) {
   m.def("fill_pattern", &fill_pattern, "NT fill with a memcheck pattern",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("buf"), py::arg("pattern"), py::arg("seed"),
-        py::arg("blocks") = 0);
+        py::arg("blocks") = 0, py::arg("first_vector") = 0);
   m.def("verify_pattern", &verify_pattern,
         "verify a memcheck pattern -> (mismatched_words, first_bad_word, "
         "bad_bits_mask, records)",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("buf"), py::arg("pattern"), py::arg("seed"),
-        py::arg("max_records") = 16, py::arg("blocks") = 0);
+        py::arg("max_records") = 16, py::arg("blocks") = 0,
+        py::arg("first_vector") = 0);
   m.def("verify_then_fill", &verify_then_fill,
         "fused verify(expect_pattern) + fill(next_pattern) pass",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("buf"), py::arg("expect_pattern"), py::arg("next_pattern"),
-        py::arg("seed"), py::arg("max_records") = 16, py::arg("blocks") = 0);
+        py::arg("seed"), py::arg("max_records") = 16, py::arg("blocks") = 0,
+        py::arg("first_vector") = 0);
 }

@@ -2,8 +2,9 @@
 // kernels that stream a buffer: memcheck.hip (HBM) and hostlink.hip
 // (host memory over the PCIe link); both files compile into _gpuprobe.
 //
-// Patterns (v = 64-bit index of a 16 B vector from the buffer's first
-// byte, j = 32-bit word inside it, ids 0..5, odd id = ~(even id)):
+// Patterns (v = 64-bit vector index: the caller's first_vector, 0 by
+// default, plus the index of a 16 B vector from the buffer's first
+// byte; j = 32-bit word inside it, ids 0..5, odd id = ~(even id)):
 //   0/1 addr     h = fmix32(lo32(v) ^ hi32(v)*0x9E3779B9 ^ seed)
 //                word[j] = rotl32(h, 8j) ^ K[j]
 //   2/3 checker  c = v even ? 0xAAAAAAAA : 0x55555555; word[j] = j even ? c : ~c

@@ -47,6 +47,7 @@ from .memcheck import (
     VerifyResult,
     _child_lock,
     _to_result,
+    first_vector_arg,
     idle_gpus,
     pattern_id,
     reference_words,
@@ -98,35 +99,44 @@ def alloc(nbytes: int, device=None):
     return _ext().hostlink_alloc(int(nbytes), _device_index(device))
 
 
-def fill_pattern(host, pattern: Pattern, seed: int = 0, device=None, blocks: int = 0) -> None:
+def fill_pattern(host, pattern: Pattern, seed: int = 0, device=None, blocks: int = 0,
+                 first_vector: int = 0) -> None:
     """The GPU stores a pattern straight into a pinned CPU tensor
-    (contiguous, 16-byte aligned, nbytes a positive multiple of 16),
-    indexed from the tensor's own first byte.  Returns after the kernel
-    has finished.  A pageable tensor raises RuntimeError."""
-    _ext().hostlink_fill(host, pattern_id(pattern), int(seed), _device_index(device),
-                         int(blocks))
+    (contiguous, 16-byte aligned, nbytes a positive multiple of 16).
+    The tensor's own first byte is vector ``first_vector`` of the
+    pattern; first_vector + nbytes/16 may be at most 2**63.  Returns
+    after the kernel has finished.  A pageable tensor raises
+    RuntimeError."""
+    pid, first = pattern_id(pattern), first_vector_arg(first_vector)
+    _ext().hostlink_fill(host, pid, int(seed), _device_index(device), int(blocks), first)
 
 
 def verify_pattern(host, pattern: Pattern, seed: int = 0, device=None,
-                   max_records: int = 16, blocks: int = 0) -> VerifyResult:
+                   max_records: int = 16, blocks: int = 0,
+                   first_vector: int = 0) -> VerifyResult:
     """The GPU loads a pinned CPU tensor and compares every word with
-    the pattern."""
+    the pattern counted from ``first_vector``.  Reported word indices
+    and offsets are from the tensor's first byte."""
+    pid, first = pattern_id(pattern), first_vector_arg(first_vector)
     return _to_result(_ext().hostlink_verify(
-        host, pattern_id(pattern), int(seed), _device_index(device), int(max_records),
-        int(blocks)))
+        host, pid, int(seed), _device_index(device), int(max_records), int(blocks), first))
 
 
 def duplex(read_host, read_pattern: Pattern, write_host, write_pattern: Pattern,
            seed: int = 0, device=None, max_records: int = 16,
-           read_blocks: int = 0, write_blocks: int = 0) -> VerifyResult:
+           read_blocks: int = 0, write_blocks: int = 0,
+           read_first_vector: int = 0, write_first_vector: int = 0) -> VerifyResult:
     """One launch that verifies ``read_host`` while it fills
     ``write_host``, so both directions of the link carry traffic at
     once.  The two tensors must not overlap; each is indexed from its
-    own first byte.  Returns the verify result of the read side."""
+    own first byte, plus its own ``*_first_vector`` for the pattern.
+    Returns the verify result of the read side."""
+    rpid, wpid = pattern_id(read_pattern), pattern_id(write_pattern)
+    rfirst = first_vector_arg(read_first_vector, "read_first_vector")
+    wfirst = first_vector_arg(write_first_vector, "write_first_vector")
     return _to_result(_ext().hostlink_duplex(
-        read_host, pattern_id(read_pattern), write_host, pattern_id(write_pattern),
-        int(seed), _device_index(device), int(max_records), int(read_blocks),
-        int(write_blocks)))
+        read_host, rpid, write_host, wpid, int(seed), _device_index(device),
+        int(max_records), int(read_blocks), int(write_blocks), rfirst, wfirst))
 
 
 # -- PCIe link state -------------------------------------------------------------

@@ -9,8 +9,9 @@ sequence over one buffer taken from free VRAM and reports every 32-bit
 word that read back wrong.
 
 Patterns (csrc/memcheck.hip; ``reference_words`` is the numpy
-definition): ``v`` is the 64-bit index of a 16-byte vector from the
-buffer's first byte, ``j = 0..3`` the 32-bit word inside it.
+definition): ``v`` is the 64-bit index of a 16-byte vector, counted
+from the buffer's first byte plus the caller's ``first_vector`` (0 by
+default and in ``memcheck()``), ``j = 0..3`` the 32-bit word inside it.
 
   0 addr / 1 addr_inv      h = fmix32(lo32(v) ^ hi32(v)*0x9E3779B9 ^ seed)
                            word[j] = rotl32(h, 8j) ^ K[j]
@@ -132,18 +133,35 @@ def _ext():
     return load_ext(required=True)
 
 
-def fill_pattern(buf, pattern: Pattern, seed: int = 0, blocks: int = 0) -> None:
+def first_vector_arg(first_vector: int, name: str = "first_vector") -> int:
+    """A caller's first_vector as an int; negative raises ValueError
+    before the extension is loaded."""
+    first_vector = int(first_vector)
+    if first_vector < 0:
+        raise ValueError(f"{name} must not be negative, got {first_vector}")
+    return first_vector
+
+
+def fill_pattern(buf, pattern: Pattern, seed: int = 0, blocks: int = 0,
+                 first_vector: int = 0) -> None:
     """Fill a contiguous GPU tensor (nbytes a positive multiple of 16)
-    with a pattern, indexed from the tensor's own first byte."""
-    _ext().fill_pattern(buf, pattern_id(pattern), int(seed), int(blocks))
+    with a pattern.  The tensor's own first byte is vector
+    ``first_vector`` of the pattern (``reference_words(first_vector,
+    ...)``); first_vector + nbytes/16 may be at most 2**63."""
+    pid, first = pattern_id(pattern), first_vector_arg(first_vector)
+    _ext().fill_pattern(buf, pid, int(seed), int(blocks), first)
 
 
 def verify_pattern(
-    buf, pattern: Pattern, seed: int = 0, max_records: int = 16, blocks: int = 0
+    buf, pattern: Pattern, seed: int = 0, max_records: int = 16, blocks: int = 0,
+    first_vector: int = 0,
 ) -> VerifyResult:
-    """Read the buffer back and compare every word with the pattern."""
+    """Read the buffer back and compare every word with the pattern
+    counted from ``first_vector``.  Reported word indices and offsets
+    are from the buffer start whatever first_vector is."""
+    pid, first = pattern_id(pattern), first_vector_arg(first_vector)
     return _to_result(
-        _ext().verify_pattern(buf, pattern_id(pattern), int(seed), int(max_records), int(blocks))
+        _ext().verify_pattern(buf, pid, int(seed), int(max_records), int(blocks), first)
     )
 
 
@@ -154,13 +172,16 @@ def verify_then_fill(
     seed: int = 0,
     max_records: int = 16,
     blocks: int = 0,
+    first_vector: int = 0,
 ) -> VerifyResult:
     """One fused read-check-write pass: verify expect_pattern, leave
-    next_pattern in every word whether or not it matched."""
+    next_pattern in every word whether or not it matched.  Both
+    patterns count from ``first_vector``."""
+    epid, npid = pattern_id(expect_pattern), pattern_id(next_pattern)
+    first = first_vector_arg(first_vector)
     return _to_result(
         _ext().verify_then_fill(
-            buf, pattern_id(expect_pattern), pattern_id(next_pattern),
-            int(seed), int(max_records), int(blocks),
+            buf, epid, npid, int(seed), int(max_records), int(blocks), first,
         )
     )
 

@@ -96,6 +96,88 @@ def test_addr_is_continuous_across_2_pow_32_vectors():
     assert not np.array_equal(w[3], reference_words(1, 1, "addr", 9))
 
 
+# -- the 64-bit vector index ------------------------------------------------------
+
+M32 = 0xFFFFFFFF
+# where the index arithmetic changes: the walk family's u32 `v << 2` wraps;
+# lo32 wraps and hi32 becomes 1; hi32 * golden wraps; 4v wraps u64; the
+# largest hi32 an int64 first_vector reaches
+BOUNDARIES = (1 << 30, 1 << 32, 1 << 33, 1 << 62, 0x7FFFFFFF << 32)
+
+
+def scalar_words(v, pid, seed):
+    """The four words of vector v straight from the module docstring's
+    formulas, in Python ints masked to 32 bits."""
+    def fmix32(h):
+        h ^= h >> 16
+        h = (h * 0x85EBCA6B) & M32
+        h ^= h >> 13
+        h = (h * 0xC2B2AE35) & M32
+        h ^= h >> 16
+        return h
+
+    def rotl32(x, r):
+        return ((x << r) | (x >> (32 - r))) & M32
+
+    family = pid >> 1
+    if family == 0:
+        lo, hi = v & M32, (v >> 32) & M32
+        h = fmix32(lo ^ ((hi * 0x9E3779B9) & M32) ^ seed)
+        k = (0x00000000, 0x9E3779B9, 0x7F4A7C15, 0xF39CC060)
+        w = [rotl32(h, 8 * j) ^ k[j] for j in range(4)]
+    elif family == 1:
+        c = 0xAAAAAAAA if v % 2 == 0 else 0x55555555
+        w = [c if j % 2 == 0 else c ^ M32 for j in range(4)]
+    else:
+        w = [1 << ((4 * v + j + seed) % 32) for j in range(4)]
+    return [x ^ M32 for x in w] if pid & 1 else w
+
+
+@pytest.mark.parametrize("seed", [0, 0xDEADBEEF])
+@pytest.mark.parametrize("pid", range(6))
+def test_reference_matches_scalar_definition_across_index_boundaries(pid, seed):
+    """Pins reference_words independently of numpy's integer promotion."""
+    for first in (0,) + tuple(b - 4 for b in BOUNDARIES):
+        got = reference_words(first, 8, pid, seed)
+        assert got.dtype == np.uint32 and got.shape == (32,)
+        want = [w for v in range(first, first + 8) for w in scalar_words(v, pid, seed)]
+        assert [int(x) for x in got] == want, (hex(first), pid, seed)
+
+
+@pytest.mark.parametrize("seed", [0, 0xDEADBEEF])
+@pytest.mark.parametrize("v", [5, (1 << 32) - 3])
+def test_addr_tells_v_from_v_plus_2_pow_32(v, seed):
+    n = 64
+    a = reference_words(v, n, "addr", seed).reshape(n, 4)
+    b = reference_words(v + (1 << 32), n, "addr", seed).reshape(n, 4)
+    assert (a[:, 0] != b[:, 0]).all()
+
+
+def test_negative_first_vector_is_rejected_before_the_extension_loads(monkeypatch):
+    from kubegpu_amd.probe import hostlink as hl
+
+    def no_ext():
+        raise AssertionError("the extension must not be loaded for a bad first_vector")
+
+    monkeypatch.setattr(mc, "_ext", no_ext)
+    monkeypatch.setattr(hl, "_ext", no_ext)
+    calls = [
+        lambda: mc.fill_pattern(None, "addr", 0, first_vector=-1),
+        lambda: mc.verify_pattern(None, "addr", 0, first_vector=-1),
+        lambda: mc.verify_then_fill(None, "addr", "walk1", 0, first_vector=-1),
+        lambda: hl.fill_pattern(None, "addr", 0, first_vector=-1),
+        lambda: hl.verify_pattern(None, "addr", 0, first_vector=-1),
+        lambda: hl.duplex(None, "addr", None, "addr", 0, read_first_vector=-1),
+        lambda: hl.duplex(None, "addr", None, "addr", 0, write_first_vector=-1),
+    ]
+    for call in calls:
+        with pytest.raises(ValueError, match="first_vector"):
+            call()
+    # a good value gets as far as the extension
+    with pytest.raises(AssertionError):
+        mc.fill_pattern(None, "addr", 0, first_vector=1 << 62)
+
+
 # -- manager verdicts ------------------------------------------------------------
 
 def _mgr():
