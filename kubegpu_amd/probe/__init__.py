@@ -10,7 +10,11 @@ from .bandwidth import (  # noqa: F401
     read_sum,
     write_bw_gbps,
 )
-from .rccl_probe import run_rccl_probe, torch_allreduce_busbw  # noqa: F401
+from .rccl_probe import (  # noqa: F401
+    RcclProbeCheckFailed,
+    run_rccl_probe,
+    torch_allreduce_busbw,
+)
 from .xgmi_counters import (  # noqa: F401
     diff_link_metrics,
     probe_with_link_utilization,

@@ -134,6 +134,10 @@ def test_rcclprobe_binary():
     rec = json.loads(out.stdout.decode().strip().splitlines()[-1])
     assert rec["ndev"] == 1
     assert rec["busbw_gbps"] > 0
+    # every element of recv and send was verified on the GPU
+    assert rec["check"] == "pass"
+    assert rec["mismatches"] == 0
+    assert rec["checked_elements"] == 2 * (64 << 20) // 2
 
 
 def test_graft_smoke():
@@ -290,6 +294,8 @@ def test_rcclprobe_across_all_gpus_when_multi():
     rec = run_rccl_probe(devices=idxs, nbytes=256 << 20, iters=10, warmup=3,
                          timeout_s=420)
     assert rec["check"] == "pass"
+    assert rec["mismatches"] == 0
+    assert rec["checked_elements"] == 2 * n * (256 << 20) // 2
     assert rec["ndev"] == n
     # xGMI ring floor: well below one link (~153 GB/s) means the ring
     # fell back to host paths — the placement model would be wrong
