@@ -7,9 +7,11 @@ Artifacts (all inside the package so they ship with the repo snapshot):
 * _schedcore*.so        — pybind11 scheduler hot path (g++)
 * _ext/_gpuprobe*.so    — torch extension with CDNA4 bandwidth, HBM
                           integrity (memcheck), compute-unit integrity
-                          (cucheck) and host-link integrity (hostlink)
+                          (cucheck), matrix-core format integrity
+                          (mxcheck) and host-link integrity (hostlink)
                           kernels; memcheck and hostlink share
-                          csrc/pattern_common.h
+                          csrc/pattern_common.h, cucheck and mxcheck
+                          csrc/cucheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
 Rebuilds are skipped when the artifact is newer than its sources, the
@@ -88,13 +90,14 @@ def build_gpuprobe(verbose: bool = True) -> str:
     os.environ.setdefault("PYTORCH_ROCM_ARCH", GFX_ARCH)
     os.makedirs(EXT_DIR, exist_ok=True)
     # bandwidth kernels + HBM integrity (memcheck) kernels + compute-unit
-    # integrity (cucheck) kernel + host-link integrity (hostlink)
-    # kernels, one module
+    # integrity (cucheck) kernel + matrix-core format integrity (mxcheck)
+    # kernel + host-link integrity (hostlink) kernels, one module
     srcs = [os.path.join(CSRC, name)
             for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip",
-                         "hostlink.hip")]
+                         "mxcheck.hip", "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
-    deps = srcs + [os.path.join(CSRC, "pattern_common.h")]
+    deps = srcs + [os.path.join(CSRC, name)
+                   for name in ("pattern_common.h", "cucheck_common.h")]
     suffix = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(EXT_DIR, "_gpuprobe" + suffix)
     alt = os.path.join(EXT_DIR, "_gpuprobe.so")

@@ -8,12 +8,16 @@ Modes:
   amddevs --schedule K    schedule a synthetic K-GPU pod against the local
                           node and print the chosen GPU set + allocation
   amddevs --probe K       same, then run the in-pod RCCL probe over the set
-  amddevs --health        per-GPU health view (ECC totals, tombstones)
+  amddevs --health        per-GPU health view (ECC totals, tombstones,
+                          the active probes' verdicts)
   amddevs --memcheck      HBM integrity probe over the idle GPUs, one child
                           process per GPU; prints {uuid: result}
                           (exit 1 = mismatches, 2 = nothing could run)
   amddevs --cucheck       compute-unit integrity probe over the idle GPUs,
                           same shape and exit codes ([--rounds N])
+  amddevs --mxcheck       matrix-core format (f16, fp8, MXFP4, f64) integrity
+                          probe over the idle GPUs, same shape and exit
+                          codes ([--rounds N])
   amddevs --hostlink      host-link (PCIe path) integrity and bandwidth
                           probe over the idle GPUs, same shape and exit
                           codes ([--bytes N])
@@ -50,8 +54,12 @@ def main(argv=None) -> int:
                    help="run the compute-unit integrity probe on every GPU "
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
-                   help="with --cucheck: rounds per GPU (default: the "
-                        "probe's own, about 0.5 s)")
+                   help="with --cucheck or --mxcheck: rounds per GPU "
+                        "(default: the probe's own, about 0.5 s)")
+    p.add_argument("--mxcheck", action="store_true",
+                   help="run the matrix-core format integrity probe (f16, fp8, "
+                        "MXFP4, f64) on every GPU this command can see no "
+                        "allocation on")
     p.add_argument("--hostlink", action="store_true",
                    help="run the host-link integrity and bandwidth probe on "
                         "every GPU this command can see no allocation on")
@@ -145,6 +153,35 @@ def main(argv=None) -> int:
             print("cucheck: no idle GPU could be checked", file=sys.stderr)
             return EXIT_CANNOT_RUN
         return 0
+    if args.mxcheck:
+        from ..probe.mxcheck import (
+            DEFAULT_ROUNDS,
+            EXIT_CANNOT_RUN,
+            mxcheck_round,
+            run_mxcheck_subprocess,
+        )
+
+        if args.fake:
+            print("--mxcheck needs real GPUs; the --fake fixture backend "
+                  "has no matrix cores to test", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        mgr = create_device_plugin(backend)
+        mgr.start()
+        # as for --memcheck: an operator asked, and raw process_count is
+        # not occupancy, so it does not gate the run
+        results = mxcheck_round(
+            mgr, run_mxcheck_subprocess, None,
+            args.rounds if args.rounds is not None else DEFAULT_ROUNDS,
+            max_process_count=None,
+        )
+        print(json.dumps(results, indent=1))
+        ran = [r for r in results.values() if "mismatches" in r]
+        if any(r["mismatches"] for r in ran):
+            return 1
+        if not ran:
+            print("mxcheck: no idle GPU could be checked", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        return 0
     if args.hostlink:
         from ..probe.hostlink import (
             DEFAULT_BYTES,
@@ -188,6 +225,7 @@ def main(argv=None) -> int:
                 "ecc_correctable": g.ecc_correctable if g else None,
                 "ecc_uncorrectable": g.ecc_uncorrectable if g else None,
                 "process_count": g.process_count if g else None,
+                "mxcheck": mgr.mxcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

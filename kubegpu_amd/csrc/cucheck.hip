@@ -20,87 +20,17 @@
 // coverage (waves_on) instead of assuming it.  Workgroups share nothing,
 // waves of a workgroup share only the LDS allocation.
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-#include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
+#include "cucheck_common.h"
+// named here too: the extension build rewrites a source with kernel
+// launches that does not include the runtime header itself
 #include <hip/hip_runtime.h>
 
-#include <tuple>
-#include <vector>
-
-#define WAVE 64
-#define CU_BLOCK 1024
-#define CU_WAVES (CU_BLOCK / WAVE)
-#define N_STAGES 4
-#define MAX_ROUNDS 65536
-#define MAX_BLOCKS 4096
-#define MAX_LDS_BYTES 163840
-#define LDS_STEP 4096
-#define MAX_RECORDS_LIMIT 4096
-#define NO_INJECT 0xFFFFFFFFu
-
-typedef unsigned int u32;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// Result block in device memory (u32 slots): header, the per-CU wave
-// table indexed xcc<<7 | se<<5 | sh<<4 | cu, then max_records records
-// of six u32 each: {global wave, xcc<<16 | HW_ID[15:0], round, stage,
-// expected, got}.
-#define RES_COUNT 0
-#define RES_FIRST 1
-#define RES_MASK 2
-#define RES_CLAIM 3
-#define RES_WAVES_ON 4
-#define WAVES_ON_SIZE 1024
-#define RES_RECORDS (RES_WAVES_ON + WAVES_ON_SIZE)
-#define RECORD_WORDS 6
-
-__device__ __forceinline__ u32 cu_fmix32(u32 h) {
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
 
 __device__ __forceinline__ u32 cu_rotl32(u32 x, int r) {
   return (x << r) | (x >> (32 - r));
-}
-
-__device__ __forceinline__ u32 cu_base(u32 seed, u32 stage, u32 r) {
-  return cu_fmix32(seed ^ ((stage + 1u) * 0x9E3779B9u) ^ (r * 0x7F4A7C15u));
-}
-
-__device__ __forceinline__ u32 cu_salt(u32 n) { return (n + 1u) * 0x9E3779B9u; }
-
-__device__ __forceinline__ u32 wave_sum(u32 v) {
-  for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-  return v;
-}
-
-// Mismatch path only (never taken on a healthy GPU): count, lowest bad
-// round, stage bits and one log slot; slots past max_records are
-// dropped, the count is not.
-__device__ __noinline__ void log_mismatch(u32* __restrict__ res, int max_records,
-                                          u32 gwave, u32 hw, u32 round, u32 stage,
-                                          u32 expected, u32 got) {
-  atomicAdd(&res[RES_COUNT], 1u);
-  atomicMin(&res[RES_FIRST], round);
-  atomicOr(&res[RES_MASK], 1u << stage);
-  u32 slot = atomicAdd(&res[RES_CLAIM], 1u);
-  if (slot < (u32)max_records) {
-    u32* rec = res + RES_RECORDS + (size_t)slot * RECORD_WORDS;
-    rec[0] = gwave;
-    rec[1] = hw;
-    rec[2] = round;
-    rec[3] = stage;
-    rec[4] = expected;
-    rec[5] = got;
-  }
 }
 
 // bf16 of a signed byte: every integer in [-128, 127] has at most eight
@@ -109,19 +39,6 @@ __device__ __forceinline__ __bf16 byte_to_bf16(u32 w, int b) {
   float f = (float)(int)(signed char)(w >> (8 * b));
   unsigned short bits = (unsigned short)(__float_as_uint(f) >> 16);
   return __builtin_bit_cast(__bf16, bits);
-}
-
-// Fold of a 32x32 accumulator tile.  C/D map of the 32x32 MFMAs: lane l,
-// register g holds row (g&3) + 8*(g>>2) + 4*(l>>5), column l&31.
-template <typename ACC>
-__device__ __forceinline__ u32 fold_tile(const ACC& acc, int lane) {
-  u32 col = lane & 31, half = lane >> 5, d = 0;
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    u32 row = (g & 3) + 8 * (g >> 2) + 4 * half;
-    d += cu_fmix32((u32)(int)acc[g] + cu_salt(32 * row + col));
-  }
-  return wave_sum(d);
 }
 
 __global__ void __launch_bounds__(CU_BLOCK)
@@ -134,15 +51,7 @@ cucheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
   const int lane = threadIdx.x % WAVE;
   const u32 wib = threadIdx.x / WAVE;
   const u32 gwave = blockIdx.x * CU_WAVES + wib;
-  // where the hardware says this wave runs, read once
-  const u32 hw_id = __builtin_amdgcn_s_getreg(GETREG_IMMED(32 - 1, 0, HW_ID));
-  const u32 xcc = __builtin_amdgcn_s_getreg(
-      GETREG_IMMED(XCC_ID_XCC_ID_SIZE - 1, XCC_ID_XCC_ID_OFFSET, XCC_ID));
-  const u32 hw = (xcc << 16) | (hw_id & 0xFFFFu);
-  if (lane == 0) {
-    u32 cu = (hw_id >> 8) & 0xFu, sh = (hw_id >> 12) & 1u, se = (hw_id >> 13) & 3u;
-    atomicAdd(&res[RES_WAVES_ON + (((xcc & 7u) << 7) | (se << 5) | (sh << 4) | cu)], 1u);
-  }
+  const u32 hw = cu_locate_wave(res, lane);
 
   // operand maps: lane l owns row l&31 of A and column l&31 of B; the
   // k a fragment slot stands for is the same for A and B, and C = A*B
@@ -247,69 +156,17 @@ cucheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
 
 // ---------------------------------------------------------------- host
 
-// global wave, packed hw id, round, stage, expected, got
-typedef std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> CuRecord;
-typedef std::tuple<int64_t, int64_t, int64_t, std::vector<CuRecord>,
-                   std::vector<int64_t>, double> CucheckOut;
-typedef std::tuple<int64_t, int64_t, int64_t, int64_t> CuInject;
-
 CucheckOut cucheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
                        int64_t blocks_arg, int64_t lds_bytes, int64_t max_records,
                        c10::optional<at::Tensor> dump,
                        c10::optional<CuInject> inject) {
-  TORCH_CHECK(rounds >= 1 && rounds <= MAX_ROUNDS, "cucheck: rounds must be in 1..",
-              MAX_ROUNDS, ", got ", rounds);
-  TORCH_CHECK(blocks_arg >= 0 && blocks_arg <= MAX_BLOCKS,
-              "cucheck: blocks must be in 0..", MAX_BLOCKS, ", got ", blocks_arg);
   TORCH_CHECK(lds_bytes >= LDS_STEP && lds_bytes <= MAX_LDS_BYTES &&
                   lds_bytes % LDS_STEP == 0,
               "cucheck: lds_bytes must be a multiple of ", LDS_STEP, " in ", LDS_STEP,
               "..", MAX_LDS_BYTES, ", got ", lds_bytes);
-  TORCH_CHECK(max_records >= 0 && max_records <= MAX_RECORDS_LIMIT,
-              "cucheck: max_records must be in 0..", MAX_RECORDS_LIMIT);
-  TORCH_CHECK(seed_arg >= 0 && seed_arg <= 0xFFFFFFFFLL, "cucheck: seed must be a u32");
-  TORCH_CHECK(expected.is_cuda(), "cucheck: expected must be on GPU");
-  TORCH_CHECK(expected.scalar_type() == at::kInt && expected.is_contiguous(),
-              "cucheck: expected must be a contiguous int32 tensor");
-  TORCH_CHECK(expected.numel() == rounds * N_STAGES, "cucheck: expected must hold ",
-              rounds * N_STAGES, " elements (rounds x 4), got ", expected.numel());
-
+  CuLaunch l = cu_prepare("cucheck", expected, seed_arg, rounds, blocks_arg,
+                          max_records, dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
-  int64_t blocks = blocks_arg;
-  if (blocks == 0)
-    blocks = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-  TORCH_CHECK(blocks >= 1 && blocks <= MAX_BLOCKS, "cucheck: default grid ", blocks,
-              " out of range");
-
-  u32* dump_ptr = nullptr;
-  if (dump.has_value()) {
-    const at::Tensor& d = *dump;
-    TORCH_CHECK(d.is_cuda() && d.get_device() == expected.get_device(),
-                "cucheck: dump must be on the same GPU as expected");
-    TORCH_CHECK(d.scalar_type() == at::kInt && d.is_contiguous(),
-                "cucheck: dump must be a contiguous int32 tensor");
-    TORCH_CHECK(d.numel() == blocks * CU_WAVES * rounds * N_STAGES,
-                "cucheck: dump must hold ", blocks * CU_WAVES * rounds * N_STAGES,
-                " elements (waves x rounds x 4), got ", d.numel());
-    dump_ptr = (u32*)d.data_ptr();
-  }
-
-  u32 inj_wave = NO_INJECT, inj_round = 0, inj_stage = 0, inj_mask = 0;
-  if (inject.has_value()) {
-    int64_t w = std::get<0>(*inject), r = std::get<1>(*inject);
-    int64_t s = std::get<2>(*inject), m = std::get<3>(*inject);
-    TORCH_CHECK(w >= 0 && w < blocks * CU_WAVES && r >= 0 && r < rounds && s >= 0 &&
-                    s < N_STAGES && m >= 0 && m <= 0xFFFFFFFFLL,
-                "cucheck: inject (wave, round, stage, mask) out of range");
-    inj_wave = (u32)w;
-    inj_round = (u32)r;
-    inj_stage = (u32)s;
-    inj_mask = (u32)m;
-  }
-
-  at::Tensor res = at::zeros({RES_RECORDS + RECORD_WORDS * max_records},
-                             expected.options().dtype(at::kInt));
-  res.select(0, RES_FIRST).fill_(-1);  // u32 max: identity for atomicMin
 
   // more than 64 KiB of dynamic LDS has to be asked for
   C10_HIP_CHECK(hipFuncSetAttribute((const void*)cucheck_kernel,
@@ -320,12 +177,11 @@ CucheckOut cucheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
   C10_HIP_CHECK(hipEventCreate(&t0));
   C10_HIP_CHECK(hipEventCreate(&t1));
   C10_HIP_CHECK(hipEventRecord(t0, stream));
-  hipLaunchKernelGGL(cucheck_kernel, dim3((unsigned)blocks), dim3(CU_BLOCK),
+  hipLaunchKernelGGL(cucheck_kernel, dim3((unsigned)l.blocks), dim3(CU_BLOCK),
                      (size_t)lds_bytes, stream, (u32)seed_arg, (u32)rounds,
-                     (const u32*)expected.data_ptr(), (u32*)res.data_ptr(),
-                     (int)max_records, dump_ptr,
-                     (u32)(lds_bytes / 4 / CU_WAVES), inj_wave, inj_round, inj_stage,
-                     inj_mask);
+                     (const u32*)expected.data_ptr(), (u32*)l.res.data_ptr(),
+                     (int)max_records, l.dump, (u32)(lds_bytes / 4 / CU_WAVES),
+                     l.inj_wave, l.inj_round, l.inj_stage, l.inj_mask);
   hipError_t launch_err = hipGetLastError();
   (void)hipEventRecord(t1, stream);
   hipError_t sync_err = hipEventSynchronize(t1);
@@ -335,22 +191,7 @@ CucheckOut cucheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
   (void)hipEventDestroy(t1);
   C10_HIP_CHECK(launch_err);
   C10_HIP_CHECK(sync_err);
-
-  at::Tensor host = res.cpu();
-  const u32* p = (const u32*)host.data_ptr<int32_t>();
-  int64_t claimed = p[RES_CLAIM];
-  int64_t n = claimed < max_records ? claimed : max_records;
-  std::vector<CuRecord> records;
-  records.reserve((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    const u32* rec = p + RES_RECORDS + RECORD_WORDS * i;
-    records.emplace_back(rec[0], rec[1], rec[2], rec[3], rec[4], rec[5]);
-  }
-  std::vector<int64_t> waves_on(p + RES_WAVES_ON, p + RES_WAVES_ON + WAVES_ON_SIZE);
-  int64_t count = p[RES_COUNT];
-  int64_t first = count ? (int64_t)p[RES_FIRST] : -1;
-  return CucheckOut(count, first, (int64_t)p[RES_MASK], std::move(records),
-                    std::move(waves_on), (double)ms / 1e3);
+  return cu_read_result(l.res, max_records, (double)ms / 1e3);
 }
 
 // Called from gpuprobe.hip's PYBIND11_MODULE; GIL released like the

@@ -418,12 +418,15 @@ double read_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
 void bind_memcheck(py::module_& m);
 // Compute-unit integrity kernel (cucheck.hip, same extension).
 void bind_cucheck(py::module_& m);
+// Matrix-core format integrity kernel (mxcheck.hip, same extension).
+void bind_mxcheck(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_memcheck(m);
   bind_cucheck(m);
+  bind_mxcheck(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

@@ -94,6 +94,8 @@ class AMDGPUManager(Device):
         self.memcheck: Dict[str, dict] = {}
         # Active compute-unit integrity (cucheck) verdicts, kept the same way.
         self.cucheck: Dict[str, dict] = {}
+        # Active matrix-core format integrity (mxcheck) verdicts, kept the same way.
+        self.mxcheck: Dict[str, dict] = {}
         # Active host-link integrity (hostlink) verdicts, kept the same way.
         self.hostlink: Dict[str, dict] = {}
 
@@ -189,6 +191,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                     self.memcheck.pop(uuid, None)
                     self.cucheck.pop(uuid, None)
+                    self.mxcheck.pop(uuid, None)
                     self.hostlink.pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
@@ -201,8 +204,8 @@ class AMDGPUManager(Device):
         """uuid -> healthy for every advertisable device.
 
         Present GPUs are healthy unless they report uncorrectable ECC
-        errors (GpuInfo.healthy) or carry a failed memcheck, cucheck or
-        hostlink verdict;
+        errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
+        mxcheck or hostlink verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -215,13 +218,14 @@ class AMDGPUManager(Device):
     # -- active HBM integrity verdicts ---------------------------------------
 
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
-        """ECC health AND no failed memcheck, cucheck or hostlink verdict
-        (lock held)."""
+        """ECC health AND no failed memcheck, cucheck, mxcheck or hostlink
+        verdict (lock held)."""
         m = self.memcheck.get(gpu.uuid)
         c = self.cucheck.get(gpu.uuid)
+        x = self.mxcheck.get(gpu.uuid)
         h = self.hostlink.get(gpu.uuid)
         return gpu.healthy and (m is None or m["ok"]) and (c is None or c["ok"]) \
-            and (h is None or h["ok"])
+            and (x is None or x["ok"]) and (h is None or h["ok"])
 
     def record_memcheck(self, uuid: str, result: dict) -> bool:
         """Store a memcheck result (MemcheckResult.to_dict()) for a GPU.
@@ -294,6 +298,44 @@ class AMDGPUManager(Device):
     def cucheck_status(self, uuid: str) -> Optional[dict]:
         with self._lock:
             v = self.cucheck.get(uuid)
+            return dict(v) if v is not None else None
+
+    # -- active matrix-core format integrity verdicts ----------------------------
+
+    def record_mxcheck(self, uuid: str, result: dict) -> bool:
+        """Store an mxcheck result (MxcheckResult.to_dict()) for a GPU.
+
+        A result with mismatches marks the GPU unhealthy until a later
+        passing result or clear_mxcheck(); returns the verdict's ok
+        flag.  Unknown uuids are rejected with KeyError."""
+        mismatches = int(result.get("mismatches", 0))
+        ok = bool(result.get("ok", mismatches == 0)) and mismatches == 0
+        verdict = dict(result)
+        verdict["ok"] = ok
+        verdict["mismatches"] = mismatches
+        verdict.setdefault("timestamp", time.time())
+        with self._lock:
+            if uuid not in self.gpus and uuid not in self.vanished:
+                raise KeyError(f"unknown GPU uuid {uuid}")
+            self.mxcheck[uuid] = verdict
+        if not ok:
+            utils.errorf(
+                "mxcheck FAILED on GPU %s: %d wrong digest(s), first bad round "
+                "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
+                uuid, mismatches, verdict.get("first_bad_round"),
+                ",".join(verdict.get("bad_stages") or []) or "?",
+                ",".join(verdict.get("bad_cus") or []) or "?",
+            )
+        return ok
+
+    def clear_mxcheck(self, uuid: str) -> bool:
+        """Forget a GPU's verdict (operator override); True if one existed."""
+        with self._lock:
+            return self.mxcheck.pop(uuid, None) is not None
+
+    def mxcheck_status(self, uuid: str) -> Optional[dict]:
+        with self._lock:
+            v = self.mxcheck.get(uuid)
             return dict(v) if v is not None else None
 
     # -- active host-link integrity verdicts -------------------------------------
@@ -416,8 +458,8 @@ class AMDGPUManager(Device):
             return
         with self._lock:
             # capacity counts every discovered GPU; allocatable excludes
-            # ECC-unhealthy, memcheck-failed, cucheck-failed and
-            # hostlink-failed ones (such a GPU stays visible but must not take new pods — mirrors the
+            # ECC-unhealthy, memcheck-failed, cucheck-failed, mxcheck-failed
+            # and hostlink-failed ones (such a GPU stays visible but must not take new pods — mirrors the
             # kubelet plugin's per-device Unhealthy advertisement)
             count = len(self.gpus)
             healthy_count = sum(1 for g in self.gpus.values() if self._gpu_healthy(g))

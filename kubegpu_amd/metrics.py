@@ -37,6 +37,8 @@ class Metrics:
         self.gpu_memcheck_errors: Dict[str, int] = {}
         self.gpu_cucheck: Dict[str, dict] = {}
         self.gpu_cucheck_errors: Dict[str, int] = {}
+        self.gpu_mxcheck: Dict[str, dict] = {}
+        self.gpu_mxcheck_errors: Dict[str, int] = {}
         self.gpu_hostlink: Dict[str, dict] = {}
         self.gpu_hostlink_errors: Dict[str, int] = {}
         if _HAVE_PROM:
@@ -63,7 +65,7 @@ class Metrics:
             )
             self._gpu_health = Gauge(
                 "kubegpu_amd_gpu_healthy",
-                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck/hostlink)",
+                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck/hostlink/mxcheck)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -124,6 +126,30 @@ class Metrics:
             self._cucheck_err = Counter(
                 "kubegpu_amd_gpu_cucheck_errors_total",
                 "cucheck runs that could not complete (not a compute fault)",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._mxcheck_mismatches = Gauge(
+                "kubegpu_amd_gpu_mxcheck_mismatches",
+                "wave digests that came out wrong in the last matrix-core format mxcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._mxcheck_cus = Gauge(
+                "kubegpu_amd_gpu_mxcheck_cus_covered",
+                "distinct compute units that ran a wave of the last mxcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._mxcheck_ts = Gauge(
+                "kubegpu_amd_gpu_mxcheck_last_run_timestamp_seconds",
+                "unix time of the last completed matrix-core format mxcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._mxcheck_err = Counter(
+                "kubegpu_amd_gpu_mxcheck_errors_total",
+                "mxcheck runs that could not complete (not a matrix-core fault)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -239,6 +265,25 @@ class Metrics:
             self.gpu_cucheck_errors[uuid] = self.gpu_cucheck_errors.get(uuid, 0) + 1
         if _HAVE_PROM:
             self._cucheck_err.labels(uuid=uuid).inc()
+
+    def set_gpu_mxcheck(self, uuid: str, mismatches: int, cus_covered: int,
+                        timestamp: float) -> None:
+        with self._lock:
+            self.gpu_mxcheck[uuid] = {
+                "mismatches": int(mismatches),
+                "cus_covered": int(cus_covered),
+                "timestamp": float(timestamp),
+            }
+        if _HAVE_PROM:
+            self._mxcheck_mismatches.labels(uuid=uuid).set(float(mismatches))
+            self._mxcheck_cus.labels(uuid=uuid).set(float(cus_covered))
+            self._mxcheck_ts.labels(uuid=uuid).set(float(timestamp))
+
+    def inc_mxcheck_error(self, uuid: str) -> None:
+        with self._lock:
+            self.gpu_mxcheck_errors[uuid] = self.gpu_mxcheck_errors.get(uuid, 0) + 1
+        if _HAVE_PROM:
+            self._mxcheck_err.labels(uuid=uuid).inc()
 
     def set_gpu_hostlink(self, uuid: str, mismatches: int, h2d_gbps: float,
                          d2h_gbps: float, below_floor: bool, timestamp: float) -> None:

@@ -48,6 +48,18 @@ _CUCHECK_EXPORTS = (
 )
 
 
+# Matrix-core format integrity probe (probe/mxcheck.py), the same way;
+# the mxcheck() function is `kubegpu_amd.probe.mxcheck.mxcheck`.  Its
+# reference_digests / wave_digests stay in the submodule: the
+# package-level names are cucheck's.
+_MXCHECK_EXPORTS = (
+    "MxcheckResult",
+    "mxcheck_round",
+    "run_mxcheck_subprocess",
+    "wave_tile",
+)
+
+
 # Host-link integrity and bandwidth probe (probe/hostlink.py), the same
 # way; the hostlink() function is `kubegpu_amd.probe.hostlink.hostlink`.
 # Its fill_pattern / verify_pattern take host tensors and stay in the
@@ -69,6 +81,10 @@ def __getattr__(name):
         from . import cucheck as _cucheck
 
         return getattr(_cucheck, name)
+    if name in _MXCHECK_EXPORTS:
+        from . import mxcheck as _mxcheck
+
+        return getattr(_mxcheck, name)
     if name in _HOSTLINK_EXPORTS:
         from . import hostlink as _hostlink
 

@@ -38,8 +38,9 @@ memcheck's:
 Floating-point stages use only data for which every intermediate is an
 exactly representable integer (bytes in bf16, sums below 2**24 in f32),
 so the reference is integer arithmetic — and rounding logic is therefore
-not covered.  Nor are f64, fp8, transcendental units, or the path to
-HBM (memcheck's ground).
+not covered.  The f16, fp8, MXFP4 and f64 matrix paths are
+``probe/mxcheck.py``'s ground; transcendental units are not covered,
+nor is the path to HBM (memcheck's ground).
 
 CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
     python -m kubegpu_amd.probe.cucheck --device INDEX [--rounds N] [--seed S]

@@ -77,6 +77,18 @@ def main(argv=None) -> int:
     ap.add_argument("--cucheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the compute-unit integrity probe")
+    ap.add_argument("--mxcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the matrix-core format integrity probe (f16, "
+                         "fp8, MXFP4, f64) over the idle GPUs every SECONDS "
+                         "from the health loop; a GPU with a wrong digest "
+                         "turns Unhealthy (0 = off)")
+    ap.add_argument("--mxcheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the matrix-core format integrity "
+                         "probe (default: the probe's own, about 0.5 s)")
+    ap.add_argument("--mxcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the matrix-core format integrity probe")
     ap.add_argument("--hostlink-interval", type=float, default=0.0,
                     metavar="SECONDS",
                     help="run the host-link integrity probe over the idle "
@@ -148,6 +160,7 @@ def main(argv=None) -> int:
     watcher_started = False
     next_memcheck = time.monotonic()  # first round on the first tick
     next_cucheck = time.monotonic()
+    next_mxcheck = time.monotonic()
     next_hostlink = time.monotonic()
     while not stop["flag"]:
         if not args.no_register and not registered:
@@ -226,6 +239,23 @@ def main(argv=None) -> int:
                               max_process_count=args.cucheck_max_procs)
             except Exception as e:  # never let the probe kill the agent
                 utils.errorf("agent: cucheck round failed: %s", e)
+            plugin.servicer.notify()
+        # active matrix-core format integrity probe, same shape and the
+        # same lock
+        if args.mxcheck_interval > 0 and time.monotonic() >= next_mxcheck:
+            next_mxcheck = time.monotonic() + args.mxcheck_interval
+            try:
+                from ..probe.mxcheck import (
+                    DEFAULT_ROUNDS as MXCHECK_ROUNDS,
+                    mxcheck_round,
+                    run_mxcheck_subprocess,
+                )
+
+                mxcheck_round(manager, run_mxcheck_subprocess, METRICS,
+                              args.mxcheck_rounds or MXCHECK_ROUNDS,
+                              max_process_count=args.mxcheck_max_procs)
+            except Exception as e:  # never let the probe kill the agent
+                utils.errorf("agent: mxcheck round failed: %s", e)
             plugin.servicer.notify()
         # active host-link integrity probe, same shape and the same lock
         if args.hostlink_interval > 0 and time.monotonic() >= next_hostlink:
