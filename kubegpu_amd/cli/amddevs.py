@@ -18,6 +18,9 @@ Modes:
   amddevs --mxcheck       matrix-core format (f16, fp8, MXFP4, f64) integrity
                           probe over the idle GPUs, same shape and exit
                           codes ([--rounds N])
+  amddevs --fpcheck       IEEE rounding (f32, f64, packed f16 / f32,
+                          conversions) integrity probe over the idle GPUs,
+                          same shape and exit codes ([--rounds N])
   amddevs --hostlink      host-link (PCIe path) integrity and bandwidth
                           probe over the idle GPUs, same shape and exit
                           codes ([--bytes N])
@@ -54,12 +57,16 @@ def main(argv=None) -> int:
                    help="run the compute-unit integrity probe on every GPU "
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
-                   help="with --cucheck or --mxcheck: rounds per GPU "
+                   help="with --cucheck, --mxcheck or --fpcheck: rounds per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
                         "MXFP4, f64) on every GPU this command can see no "
                         "allocation on")
+    p.add_argument("--fpcheck", action="store_true",
+                   help="run the IEEE rounding integrity probe (f32, f64, "
+                        "packed f16 / f32, conversions) on every GPU this "
+                        "command can see no allocation on")
     p.add_argument("--hostlink", action="store_true",
                    help="run the host-link integrity and bandwidth probe on "
                         "every GPU this command can see no allocation on")
@@ -182,6 +189,35 @@ def main(argv=None) -> int:
             print("mxcheck: no idle GPU could be checked", file=sys.stderr)
             return EXIT_CANNOT_RUN
         return 0
+    if args.fpcheck:
+        from ..probe.fpcheck import (
+            DEFAULT_ROUNDS,
+            EXIT_CANNOT_RUN,
+            fpcheck_round,
+            run_fpcheck_subprocess,
+        )
+
+        if args.fake:
+            print("--fpcheck needs real GPUs; the --fake fixture backend "
+                  "has no FP units to test", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        mgr = create_device_plugin(backend)
+        mgr.start()
+        # as for --memcheck: an operator asked, and raw process_count is
+        # not occupancy, so it does not gate the run
+        results = fpcheck_round(
+            mgr, run_fpcheck_subprocess, None,
+            args.rounds if args.rounds is not None else DEFAULT_ROUNDS,
+            max_process_count=None,
+        )
+        print(json.dumps(results, indent=1))
+        ran = [r for r in results.values() if "mismatches" in r]
+        if any(r["mismatches"] for r in ran):
+            return 1
+        if not ran:
+            print("fpcheck: no idle GPU could be checked", file=sys.stderr)
+            return EXIT_CANNOT_RUN
+        return 0
     if args.hostlink:
         from ..probe.hostlink import (
             DEFAULT_BYTES,
@@ -226,6 +262,7 @@ def main(argv=None) -> int:
                 "ecc_uncorrectable": g.ecc_uncorrectable if g else None,
                 "process_count": g.process_count if g else None,
                 "mxcheck": mgr.mxcheck_status(uuid),
+                "fpcheck": mgr.fpcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

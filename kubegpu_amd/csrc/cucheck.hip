@@ -11,7 +11,8 @@
 //                      read back by another lane, complemented, read again
 // Inputs are word(stage, r, idx) = fmix32(base(seed, stage, r) + idx) cut
 // into signed bytes.  Every floating-point intermediate is an exactly
-// representable integer, so rounding logic is not covered.
+// representable integer, so rounding logic is not covered (fpcheck.hip's
+// ground).
 //
 // 1024-thread workgroups (16 waves); with the default 160 KiB of dynamic
 // LDS one workgroup fills a CU, so a grid of multiProcessorCount puts one

@@ -420,6 +420,8 @@ void bind_memcheck(py::module_& m);
 void bind_cucheck(py::module_& m);
 // Matrix-core format integrity kernel (mxcheck.hip, same extension).
 void bind_mxcheck(py::module_& m);
+// IEEE rounding integrity kernel (fpcheck.hip, same extension).
+void bind_fpcheck(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
@@ -427,6 +429,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_memcheck(m);
   bind_cucheck(m);
   bind_mxcheck(m);
+  bind_fpcheck(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

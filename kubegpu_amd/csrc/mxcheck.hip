@@ -17,7 +17,7 @@
 // from cucheck's.  Every operand is chosen so that all partial sums are
 // exactly representable in the accumulator type: the result is an integer
 // in the stage's unit whatever order the hardware sums in, and rounding
-// logic is not covered.
+// logic is not covered (fpcheck.hip's ground).
 //
 // Launch shape and accounting are cucheck's: 1024-thread workgroups (16
 // waves), grid 0 = one workgroup per CU, each wave reads HW_ID / XCC_ID

@@ -96,6 +96,8 @@ class AMDGPUManager(Device):
         self.cucheck: Dict[str, dict] = {}
         # Active matrix-core format integrity (mxcheck) verdicts, kept the same way.
         self.mxcheck: Dict[str, dict] = {}
+        # Active IEEE rounding integrity (fpcheck) verdicts, kept the same way.
+        self.fpcheck: Dict[str, dict] = {}
         # Active host-link integrity (hostlink) verdicts, kept the same way.
         self.hostlink: Dict[str, dict] = {}
 
@@ -192,6 +194,7 @@ class AMDGPUManager(Device):
                     self.memcheck.pop(uuid, None)
                     self.cucheck.pop(uuid, None)
                     self.mxcheck.pop(uuid, None)
+                    self.fpcheck.pop(uuid, None)
                     self.hostlink.pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
@@ -205,7 +208,7 @@ class AMDGPUManager(Device):
 
         Present GPUs are healthy unless they report uncorrectable ECC
         errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
-        mxcheck or hostlink verdict;
+        mxcheck, fpcheck or hostlink verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -218,14 +221,16 @@ class AMDGPUManager(Device):
     # -- active HBM integrity verdicts ---------------------------------------
 
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
-        """ECC health AND no failed memcheck, cucheck, mxcheck or hostlink
-        verdict (lock held)."""
+        """ECC health AND no failed memcheck, cucheck, mxcheck, fpcheck or
+        hostlink verdict (lock held)."""
         m = self.memcheck.get(gpu.uuid)
         c = self.cucheck.get(gpu.uuid)
         x = self.mxcheck.get(gpu.uuid)
+        f = self.fpcheck.get(gpu.uuid)
         h = self.hostlink.get(gpu.uuid)
         return gpu.healthy and (m is None or m["ok"]) and (c is None or c["ok"]) \
-            and (x is None or x["ok"]) and (h is None or h["ok"])
+            and (x is None or x["ok"]) and (f is None or f["ok"]) \
+            and (h is None or h["ok"])
 
     def record_memcheck(self, uuid: str, result: dict) -> bool:
         """Store a memcheck result (MemcheckResult.to_dict()) for a GPU.
@@ -336,6 +341,44 @@ class AMDGPUManager(Device):
     def mxcheck_status(self, uuid: str) -> Optional[dict]:
         with self._lock:
             v = self.mxcheck.get(uuid)
+            return dict(v) if v is not None else None
+
+    # -- active IEEE rounding integrity verdicts -----------------------------------
+
+    def record_fpcheck(self, uuid: str, result: dict) -> bool:
+        """Store an fpcheck result (FpcheckResult.to_dict()) for a GPU.
+
+        A result with mismatches marks the GPU unhealthy until a later
+        passing result or clear_fpcheck(); returns the verdict's ok
+        flag.  Unknown uuids are rejected with KeyError."""
+        mismatches = int(result.get("mismatches", 0))
+        ok = bool(result.get("ok", mismatches == 0)) and mismatches == 0
+        verdict = dict(result)
+        verdict["ok"] = ok
+        verdict["mismatches"] = mismatches
+        verdict.setdefault("timestamp", time.time())
+        with self._lock:
+            if uuid not in self.gpus and uuid not in self.vanished:
+                raise KeyError(f"unknown GPU uuid {uuid}")
+            self.fpcheck[uuid] = verdict
+        if not ok:
+            utils.errorf(
+                "fpcheck FAILED on GPU %s: %d wrong digest(s), first bad round "
+                "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
+                uuid, mismatches, verdict.get("first_bad_round"),
+                ",".join(verdict.get("bad_stages") or []) or "?",
+                ",".join(verdict.get("bad_cus") or []) or "?",
+            )
+        return ok
+
+    def clear_fpcheck(self, uuid: str) -> bool:
+        """Forget a GPU's verdict (operator override); True if one existed."""
+        with self._lock:
+            return self.fpcheck.pop(uuid, None) is not None
+
+    def fpcheck_status(self, uuid: str) -> Optional[dict]:
+        with self._lock:
+            v = self.fpcheck.get(uuid)
             return dict(v) if v is not None else None
 
     # -- active host-link integrity verdicts -------------------------------------
@@ -458,7 +501,7 @@ class AMDGPUManager(Device):
             return
         with self._lock:
             # capacity counts every discovered GPU; allocatable excludes
-            # ECC-unhealthy, memcheck-failed, cucheck-failed, mxcheck-failed
+            # ECC-unhealthy, memcheck-failed, cucheck-failed, mxcheck-failed, fpcheck-failed
             # and hostlink-failed ones (such a GPU stays visible but must not take new pods — mirrors the
             # kubelet plugin's per-device Unhealthy advertisement)
             count = len(self.gpus)

@@ -39,6 +39,8 @@ class Metrics:
         self.gpu_cucheck_errors: Dict[str, int] = {}
         self.gpu_mxcheck: Dict[str, dict] = {}
         self.gpu_mxcheck_errors: Dict[str, int] = {}
+        self.gpu_fpcheck: Dict[str, dict] = {}
+        self.gpu_fpcheck_errors: Dict[str, int] = {}
         self.gpu_hostlink: Dict[str, dict] = {}
         self.gpu_hostlink_errors: Dict[str, int] = {}
         if _HAVE_PROM:
@@ -65,7 +67,7 @@ class Metrics:
             )
             self._gpu_health = Gauge(
                 "kubegpu_amd_gpu_healthy",
-                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck/hostlink/mxcheck)",
+                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck/hostlink/fpcheck/mxcheck)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -150,6 +152,30 @@ class Metrics:
             self._mxcheck_err = Counter(
                 "kubegpu_amd_gpu_mxcheck_errors_total",
                 "mxcheck runs that could not complete (not a matrix-core fault)",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._fpcheck_mismatches = Gauge(
+                "kubegpu_amd_gpu_fpcheck_mismatches",
+                "wave digests that came out wrong in the last IEEE rounding fpcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._fpcheck_cus = Gauge(
+                "kubegpu_amd_gpu_fpcheck_cus_covered",
+                "distinct compute units that ran a wave of the last fpcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._fpcheck_ts = Gauge(
+                "kubegpu_amd_gpu_fpcheck_last_run_timestamp_seconds",
+                "unix time of the last completed IEEE rounding fpcheck",
+                ["uuid"],
+                registry=self.registry,
+            )
+            self._fpcheck_err = Counter(
+                "kubegpu_amd_gpu_fpcheck_errors_total",
+                "fpcheck runs that could not complete (not a rounding fault)",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -284,6 +310,25 @@ class Metrics:
             self.gpu_mxcheck_errors[uuid] = self.gpu_mxcheck_errors.get(uuid, 0) + 1
         if _HAVE_PROM:
             self._mxcheck_err.labels(uuid=uuid).inc()
+
+    def set_gpu_fpcheck(self, uuid: str, mismatches: int, cus_covered: int,
+                        timestamp: float) -> None:
+        with self._lock:
+            self.gpu_fpcheck[uuid] = {
+                "mismatches": int(mismatches),
+                "cus_covered": int(cus_covered),
+                "timestamp": float(timestamp),
+            }
+        if _HAVE_PROM:
+            self._fpcheck_mismatches.labels(uuid=uuid).set(float(mismatches))
+            self._fpcheck_cus.labels(uuid=uuid).set(float(cus_covered))
+            self._fpcheck_ts.labels(uuid=uuid).set(float(timestamp))
+
+    def inc_fpcheck_error(self, uuid: str) -> None:
+        with self._lock:
+            self.gpu_fpcheck_errors[uuid] = self.gpu_fpcheck_errors.get(uuid, 0) + 1
+        if _HAVE_PROM:
+            self._fpcheck_err.labels(uuid=uuid).inc()
 
     def set_gpu_hostlink(self, uuid: str, mismatches: int, h2d_gbps: float,
                          d2h_gbps: float, below_floor: bool, timestamp: float) -> None:

@@ -60,6 +60,17 @@ _MXCHECK_EXPORTS = (
 )
 
 
+# IEEE rounding integrity probe (probe/fpcheck.py), the same way; the
+# fpcheck() function is `kubegpu_amd.probe.fpcheck.fpcheck`.  Its
+# reference_digests / wave_digests stay in the submodule too.
+_FPCHECK_EXPORTS = (
+    "FpcheckResult",
+    "fpcheck_round",
+    "run_fpcheck_subprocess",
+    "wave_values",
+)
+
+
 # Host-link integrity and bandwidth probe (probe/hostlink.py), the same
 # way; the hostlink() function is `kubegpu_amd.probe.hostlink.hostlink`.
 # Its fill_pattern / verify_pattern take host tensors and stay in the
@@ -85,6 +96,10 @@ def __getattr__(name):
         from . import mxcheck as _mxcheck
 
         return getattr(_mxcheck, name)
+    if name in _FPCHECK_EXPORTS:
+        from . import fpcheck as _fpcheck
+
+        return getattr(_fpcheck, name)
     if name in _HOSTLINK_EXPORTS:
         from . import hostlink as _hostlink
 

@@ -38,7 +38,8 @@ memcheck's:
 Floating-point stages use only data for which every intermediate is an
 exactly representable integer (bytes in bf16, sums below 2**24 in f32),
 so the reference is integer arithmetic — and rounding logic is therefore
-not covered.  The f16, fp8, MXFP4 and f64 matrix paths are
+not covered: it is ``probe/fpcheck.py``'s ground.  The f16, fp8, MXFP4
+and f64 matrix paths are
 ``probe/mxcheck.py``'s ground; transcendental units are not covered,
 nor is the path to HBM (memcheck's ground).
 

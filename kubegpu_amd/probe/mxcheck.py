@@ -56,7 +56,7 @@ inputs differ from cucheck's:
 Every stage uses only operands for which all partial sums are exactly
 representable in the accumulator type, so the reference is integer
 arithmetic, the result does not depend on the order the hardware sums
-in — and rounding logic is not covered.
+in — and rounding logic is not covered (``probe/fpcheck.py``'s ground).
 
 How the kernel feeds the instructions (proved element by element by the
 GPU test of ``wave_tile`` against ``matmul_tile``): in the 32x32 stages

@@ -89,6 +89,18 @@ def main(argv=None) -> int:
     ap.add_argument("--mxcheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the matrix-core format integrity probe")
+    ap.add_argument("--fpcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the IEEE rounding integrity probe (f32, f64, "
+                         "packed, conversions) over the idle GPUs every "
+                         "SECONDS from the health loop; a GPU with a wrong "
+                         "digest turns Unhealthy (0 = off)")
+    ap.add_argument("--fpcheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the IEEE rounding integrity "
+                         "probe (default: the probe's own, about 0.5 s)")
+    ap.add_argument("--fpcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the IEEE rounding integrity probe")
     ap.add_argument("--hostlink-interval", type=float, default=0.0,
                     metavar="SECONDS",
                     help="run the host-link integrity probe over the idle "
@@ -161,6 +173,7 @@ def main(argv=None) -> int:
     next_memcheck = time.monotonic()  # first round on the first tick
     next_cucheck = time.monotonic()
     next_mxcheck = time.monotonic()
+    next_fpcheck = time.monotonic()
     next_hostlink = time.monotonic()
     while not stop["flag"]:
         if not args.no_register and not registered:
@@ -256,6 +269,23 @@ def main(argv=None) -> int:
                               max_process_count=args.mxcheck_max_procs)
             except Exception as e:  # never let the probe kill the agent
                 utils.errorf("agent: mxcheck round failed: %s", e)
+            plugin.servicer.notify()
+        # active IEEE rounding integrity probe, same shape and the same
+        # lock
+        if args.fpcheck_interval > 0 and time.monotonic() >= next_fpcheck:
+            next_fpcheck = time.monotonic() + args.fpcheck_interval
+            try:
+                from ..probe.fpcheck import (
+                    DEFAULT_ROUNDS as FPCHECK_ROUNDS,
+                    fpcheck_round,
+                    run_fpcheck_subprocess,
+                )
+
+                fpcheck_round(manager, run_fpcheck_subprocess, METRICS,
+                              args.fpcheck_rounds or FPCHECK_ROUNDS,
+                              max_process_count=args.fpcheck_max_procs)
+            except Exception as e:  # never let the probe kill the agent
+                utils.errorf("agent: fpcheck round failed: %s", e)
             plugin.servicer.notify()
         # active host-link integrity probe, same shape and the same lock
         if args.hostlink_interval > 0 and time.monotonic() >= next_hostlink:
