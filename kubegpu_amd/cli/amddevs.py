@@ -37,6 +37,54 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
+from ..probe._active import ACTIVE_PROBES, EXIT_CANNOT_RUN
+
+# probe -> (what the --fake backend lacks, size argument, name of its
+# default in the probe's module, result keys that count wrong data)
+_PROBE_RUNS = {
+    "memcheck": ("memory", "bytes", "DEFAULT_BYTES", ("mismatched_words",)),
+    "cucheck": ("compute units", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "mxcheck": ("matrix cores", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "fpcheck": ("FP units", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "hostlink": ("host link", "bytes", "DEFAULT_BYTES",
+                 ("mismatched_words", "cpu_sample_mismatches")),
+}
+
+
+def _run_probe(probe: str, args, backend) -> int:
+    """Run an active probe over the idle GPUs, print {uuid: result} and
+    turn the results into an exit code: 1 = wrong data on some GPU, 2 =
+    nothing could run, 0 otherwise."""
+    import importlib
+
+    lacks, size_arg, default_name, fail_keys = _PROBE_RUNS[probe]
+    if args.fake:
+        print(f"--{probe} needs real GPUs; the --fake fixture backend "
+              f"has no {lacks} to test", file=sys.stderr)
+        return EXIT_CANNOT_RUN
+    mod = importlib.import_module(f"..probe.{probe}", __package__)
+    mgr = create_device_plugin(backend)
+    mgr.start()
+    size = getattr(args, size_arg)
+    # An operator asked for this run, and a fresh manager has no
+    # allocation view.  Raw process_count is not occupancy (daemons
+    # registered on KFD make a resting node report 1-2), so it gates
+    # only memcheck and only on request; memcheck takes its buffer from
+    # free VRAM and cannot disturb a running job's data.
+    idle_only = probe == "memcheck" and args.memcheck_idle_only
+    results = getattr(mod, f"{probe}_round")(
+        mgr, getattr(mod, f"run_{probe}_subprocess"), None,
+        size if size is not None else getattr(mod, default_name),
+        max_process_count=0 if idle_only else None,
+    )
+    print(json.dumps(results, indent=1))
+    ran = [r for r in results.values() if fail_keys[0] in r]
+    if any(r.get(k) for r in ran for k in fail_keys):
+        return 1
+    if not ran:
+        print(f"{probe}: no idle GPU could be checked", file=sys.stderr)
+        return EXIT_CANNOT_RUN
+    return 0
 
 
 def main(argv=None) -> int:
@@ -100,153 +148,9 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    if args.memcheck:
-        from ..probe.memcheck import (
-            EXIT_CANNOT_RUN,
-            memcheck_round,
-            run_memcheck_subprocess,
-        )
-
-        if args.fake:
-            print("--memcheck needs real GPUs; the --fake fixture backend "
-                  "has no memory to test", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        mgr = create_device_plugin(backend)
-        mgr.start()
-        nbytes = args.bytes if args.bytes is not None else 1 << 30
-        # An operator asked for this run, and a fresh manager has no
-        # allocation view.  Raw process_count is not occupancy (daemons
-        # registered on KFD make a resting node report 1-2), so it only
-        # gates the run on request; the probe takes its buffer from free
-        # VRAM and cannot disturb a running job's data.
-        results = memcheck_round(
-            mgr, run_memcheck_subprocess, None, nbytes,
-            max_process_count=0 if args.memcheck_idle_only else None,
-        )
-        print(json.dumps(results, indent=1))
-        ran = [r for r in results.values() if "mismatched_words" in r]
-        if any(r["mismatched_words"] for r in ran):
-            return 1
-        if not ran:
-            print("memcheck: no idle GPU could be checked", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        return 0
-    if args.cucheck:
-        from ..probe.cucheck import (
-            DEFAULT_ROUNDS,
-            EXIT_CANNOT_RUN,
-            cucheck_round,
-            run_cucheck_subprocess,
-        )
-
-        if args.fake:
-            print("--cucheck needs real GPUs; the --fake fixture backend "
-                  "has no compute units to test", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        mgr = create_device_plugin(backend)
-        mgr.start()
-        # as for --memcheck: an operator asked, and raw process_count is
-        # not occupancy, so it does not gate the run
-        results = cucheck_round(
-            mgr, run_cucheck_subprocess, None,
-            args.rounds if args.rounds is not None else DEFAULT_ROUNDS,
-            max_process_count=None,
-        )
-        print(json.dumps(results, indent=1))
-        ran = [r for r in results.values() if "mismatches" in r]
-        if any(r["mismatches"] for r in ran):
-            return 1
-        if not ran:
-            print("cucheck: no idle GPU could be checked", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        return 0
-    if args.mxcheck:
-        from ..probe.mxcheck import (
-            DEFAULT_ROUNDS,
-            EXIT_CANNOT_RUN,
-            mxcheck_round,
-            run_mxcheck_subprocess,
-        )
-
-        if args.fake:
-            print("--mxcheck needs real GPUs; the --fake fixture backend "
-                  "has no matrix cores to test", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        mgr = create_device_plugin(backend)
-        mgr.start()
-        # as for --memcheck: an operator asked, and raw process_count is
-        # not occupancy, so it does not gate the run
-        results = mxcheck_round(
-            mgr, run_mxcheck_subprocess, None,
-            args.rounds if args.rounds is not None else DEFAULT_ROUNDS,
-            max_process_count=None,
-        )
-        print(json.dumps(results, indent=1))
-        ran = [r for r in results.values() if "mismatches" in r]
-        if any(r["mismatches"] for r in ran):
-            return 1
-        if not ran:
-            print("mxcheck: no idle GPU could be checked", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        return 0
-    if args.fpcheck:
-        from ..probe.fpcheck import (
-            DEFAULT_ROUNDS,
-            EXIT_CANNOT_RUN,
-            fpcheck_round,
-            run_fpcheck_subprocess,
-        )
-
-        if args.fake:
-            print("--fpcheck needs real GPUs; the --fake fixture backend "
-                  "has no FP units to test", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        mgr = create_device_plugin(backend)
-        mgr.start()
-        # as for --memcheck: an operator asked, and raw process_count is
-        # not occupancy, so it does not gate the run
-        results = fpcheck_round(
-            mgr, run_fpcheck_subprocess, None,
-            args.rounds if args.rounds is not None else DEFAULT_ROUNDS,
-            max_process_count=None,
-        )
-        print(json.dumps(results, indent=1))
-        ran = [r for r in results.values() if "mismatches" in r]
-        if any(r["mismatches"] for r in ran):
-            return 1
-        if not ran:
-            print("fpcheck: no idle GPU could be checked", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        return 0
-    if args.hostlink:
-        from ..probe.hostlink import (
-            DEFAULT_BYTES,
-            EXIT_CANNOT_RUN,
-            hostlink_round,
-            run_hostlink_subprocess,
-        )
-
-        if args.fake:
-            print("--hostlink needs real GPUs; the --fake fixture backend "
-                  "has no host link to test", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        mgr = create_device_plugin(backend)
-        mgr.start()
-        # as for --memcheck: an operator asked, and raw process_count is
-        # not occupancy, so it does not gate the run
-        results = hostlink_round(
-            mgr, run_hostlink_subprocess, None,
-            args.bytes if args.bytes is not None else DEFAULT_BYTES,
-            max_process_count=None,
-        )
-        print(json.dumps(results, indent=1))
-        ran = [r for r in results.values() if "mismatched_words" in r]
-        if any(r["mismatched_words"] or r.get("cpu_sample_mismatches") for r in ran):
-            return 1
-        if not ran:
-            print("hostlink: no idle GPU could be checked", file=sys.stderr)
-            return EXIT_CANNOT_RUN
-        return 0
+    for probe in ACTIVE_PROBES:
+        if getattr(args, probe):
+            return _run_probe(probe, args, backend)
     if args.health:
         mgr = create_device_plugin(backend)
         mgr.start()

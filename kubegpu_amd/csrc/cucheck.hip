@@ -133,22 +133,8 @@ cucheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
       dig[3] = wave_sum(d3);
     }
 
-    // test hook: one scalar compare per round
-    if (gwave == inj_wave && r == inj_round) {
-#pragma unroll
-      for (u32 st = 0; st < N_STAGES; ++st)
-        if (st == inj_stage) dig[st] ^= inj_mask;
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (u32 st = 0; st < N_STAGES; ++st) {
-        u32 want = expected[r * N_STAGES + st];
-        if (dig[st] != want)
-          log_mismatch(res, max_records, gwave, hw, r, st, want, dig[st]);
-        if (dump != nullptr)
-          dump[((size_t)gwave * rounds + r) * N_STAGES + st] = dig[st];
-      }
-    }
+    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
+                   inj_wave, inj_round, inj_stage, inj_mask);
   }
   // keep the workgroup's LDS allocated until all its waves are done
   __syncthreads();
@@ -169,30 +155,11 @@ CucheckOut cucheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
                           max_records, dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
 
-  // more than 64 KiB of dynamic LDS has to be asked for
-  C10_HIP_CHECK(hipFuncSetAttribute((const void*)cucheck_kernel,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_bytes));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipEvent_t t0, t1;
-  C10_HIP_CHECK(hipEventCreate(&t0));
-  C10_HIP_CHECK(hipEventCreate(&t1));
-  C10_HIP_CHECK(hipEventRecord(t0, stream));
-  hipLaunchKernelGGL(cucheck_kernel, dim3((unsigned)l.blocks), dim3(CU_BLOCK),
-                     (size_t)lds_bytes, stream, (u32)seed_arg, (u32)rounds,
-                     (const u32*)expected.data_ptr(), (u32*)l.res.data_ptr(),
-                     (int)max_records, l.dump, (u32)(lds_bytes / 4 / CU_WAVES),
-                     l.inj_wave, l.inj_round, l.inj_stage, l.inj_mask);
-  hipError_t launch_err = hipGetLastError();
-  (void)hipEventRecord(t1, stream);
-  hipError_t sync_err = hipEventSynchronize(t1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  C10_HIP_CHECK(launch_err);
-  C10_HIP_CHECK(sync_err);
-  return cu_read_result(l.res, max_records, (double)ms / 1e3);
+  return cu_launch_timed(cucheck_kernel, l, lds_bytes, max_records, (u32)seed_arg,
+                         (u32)rounds, (const u32*)expected.data_ptr(),
+                         (u32*)l.res.data_ptr(), (int)max_records, l.dump,
+                         (u32)(lds_bytes / 4 / CU_WAVES), l.inj_wave, l.inj_round,
+                         l.inj_stage, l.inj_mask);
 }
 
 // Called from gpuprobe.hip's PYBIND11_MODULE; GIL released like the

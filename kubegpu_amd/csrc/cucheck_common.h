@@ -1,13 +1,18 @@
-// Hashing, digest folding, mismatch accounting and launch arguments
-// shared by the integrity kernels that run one 16-wave workgroup per
-// compute unit: cucheck.hip (i8 / bf16 matrix cores, VALU, LDS) and
-// mxcheck.hip (f16 / fp8 / MXFP4 / f64 matrix cores); both files compile
-// into _gpuprobe.
+// Hashing, digest folding, the per-round compare, mismatch accounting,
+// launch arguments and the timed launch shared by the integrity kernels
+// that run one 16-wave workgroup per compute unit; all three files
+// compile into _gpuprobe and add only their stages:
+//   cucheck.hip  i8 / bf16 matrix cores, VALU, LDS (the one kernel that
+//                uses its dynamic LDS, hence its lds_dwords argument)
+//   mxcheck.hip  f16 / fp8 / MXFP4 / f64 matrix cores, and a single-wave
+//                launcher that returns one accumulator tile
+//   fpcheck.hip  IEEE rounding of the vector FP units, and a single-wave
+//                launcher that returns one round's raw result bits
 //
 // Every wave compares N_STAGES 32-bit digests per round with a table the
 // host computed in numpy.  Inputs are word(stage, r, idx) =
-// fmix32(base(seed, stage, r) + idx); probe/cucheck.py and
-// probe/mxcheck.py hold the numpy definitions.
+// fmix32(base(seed, stage, r) + idx); probe/cucheck.py, probe/mxcheck.py
+// and probe/fpcheck.py hold the numpy definitions.
 
 #pragma once
 
@@ -101,6 +106,36 @@ static __device__ __noinline__ void log_mismatch(u32* __restrict__ res, int max_
     rec[3] = stage;
     rec[4] = expected;
     rec[5] = got;
+  }
+}
+
+// End of a round, the same in every kernel: the test hook (one scalar
+// compare per round), then lane 0 compares the wave's digests with the
+// table, logs what differs and writes the dump if there is one.  The
+// hook works on a copy of the digests: on values the compiler keeps it
+// to four selects, through the caller's array it builds a branch tree
+// and allocates the kernel's registers differently.
+__device__ __forceinline__ void cu_check_round(
+    const u32 (&digests)[N_STAGES], u32 r, u32 rounds, int lane, u32 gwave, u32 hw,
+    const u32* __restrict__ expected, u32* __restrict__ res, int max_records,
+    u32* __restrict__ dump, u32 inj_wave, u32 inj_round, u32 inj_stage, u32 inj_mask) {
+  u32 dig[N_STAGES];
+#pragma unroll
+  for (u32 st = 0; st < N_STAGES; ++st) dig[st] = digests[st];
+  if (gwave == inj_wave && r == inj_round) {
+#pragma unroll
+    for (u32 st = 0; st < N_STAGES; ++st)
+      if (st == inj_stage) dig[st] ^= inj_mask;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (u32 st = 0; st < N_STAGES; ++st) {
+      u32 want = expected[r * N_STAGES + st];
+      if (dig[st] != want)
+        log_mismatch(res, max_records, gwave, hw, r, st, want, dig[st]);
+      if (dump != nullptr)
+        dump[((size_t)gwave * rounds + r) * N_STAGES + st] = dig[st];
+    }
   }
 }
 
@@ -214,4 +249,47 @@ static inline CucheckOut cu_read_result(const at::Tensor& res, int64_t max_recor
   int64_t first = count ? (int64_t)p[RES_FIRST] : -1;
   return CucheckOut(count, first, (int64_t)p[RES_MASK], std::move(records),
                     std::move(waves_on), elapsed_s);
+}
+
+// One timed launch of a digest kernel on the current stream, after
+// cu_prepare and under the caller's device guard: `args` are the
+// kernel's own.  The events are destroyed before either error is
+// raised.
+template <typename Kernel, typename... Args>
+static inline CucheckOut cu_launch_timed(Kernel kernel, const CuLaunch& l,
+                                         int64_t lds_bytes, int64_t max_records,
+                                         Args... args) {
+  // more than 64 KiB of dynamic LDS has to be asked for; a kernel that
+  // never touches it asks only to keep a second workgroup off the CU
+  C10_HIP_CHECK(hipFuncSetAttribute((const void*)kernel,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes));
+  auto stream = at::hip::getCurrentHIPStream();
+  hipEvent_t t0, t1;
+  C10_HIP_CHECK(hipEventCreate(&t0));
+  C10_HIP_CHECK(hipEventCreate(&t1));
+  C10_HIP_CHECK(hipEventRecord(t0, stream));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)l.blocks), dim3(CU_BLOCK), (size_t)lds_bytes,
+                     stream, args...);
+  hipError_t launch_err = hipGetLastError();
+  (void)hipEventRecord(t1, stream);
+  hipError_t sync_err = hipEventSynchronize(t1);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, t0, t1);
+  (void)hipEventDestroy(t0);
+  (void)hipEventDestroy(t1);
+  C10_HIP_CHECK(launch_err);
+  C10_HIP_CHECK(sync_err);
+  return cu_read_result(l.res, max_records, (double)ms / 1e3);
+}
+
+// Argument checks of the single-wave launchers (mxcheck_tile,
+// fpcheck_values).
+static inline void cu_check_wave_args(const char* who, int64_t seed_arg, int64_t stage,
+                                      int64_t round) {
+  TORCH_CHECK(seed_arg >= 0 && seed_arg <= 0xFFFFFFFFLL, who, ": seed must be a u32");
+  TORCH_CHECK(stage >= 0 && stage < N_STAGES, who, ": stage must be in 0..", N_STAGES - 1,
+              ", got ", stage);
+  TORCH_CHECK(round >= 0 && round < MAX_ROUNDS, who, ": round must be in 0..",
+              MAX_ROUNDS - 1, ", got ", round);
 }

@@ -433,22 +433,8 @@ fpcheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
     fp_stage_cvt(cu_base(seed, FP_STAGE0 + 3, rp), rp, (u32)lane, f3);
     u32 dig[N_STAGES] = {wave_sum(f0.d), wave_sum(f1.d), wave_sum(f2.d), wave_sum(f3.d)};
 
-    // test hook: one scalar compare per round
-    if (gwave == inj_wave && r == inj_round) {
-#pragma unroll
-      for (u32 st = 0; st < N_STAGES; ++st)
-        if (st == inj_stage) dig[st] ^= inj_mask;
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (u32 st = 0; st < N_STAGES; ++st) {
-        u32 want = expected[r * N_STAGES + st];
-        if (dig[st] != want)
-          log_mismatch(res, max_records, gwave, hw, r, st, want, dig[st]);
-        if (dump != nullptr)
-          dump[((size_t)gwave * rounds + r) * N_STAGES + st] = dig[st];
-      }
-    }
+    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
+                   inj_wave, inj_round, inj_stage, inj_mask);
   }
 #endif
 }
@@ -489,41 +475,16 @@ CucheckOut fpcheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
                           max_records, dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
 
-  // more than 64 KiB of dynamic LDS has to be asked for; the kernel
-  // never touches it, it only keeps a second workgroup off the CU
-  C10_HIP_CHECK(hipFuncSetAttribute((const void*)fpcheck_kernel,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    MAX_LDS_BYTES));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipEvent_t t0, t1;
-  C10_HIP_CHECK(hipEventCreate(&t0));
-  C10_HIP_CHECK(hipEventCreate(&t1));
-  C10_HIP_CHECK(hipEventRecord(t0, stream));
-  hipLaunchKernelGGL(fpcheck_kernel, dim3((unsigned)l.blocks), dim3(CU_BLOCK),
-                     (size_t)MAX_LDS_BYTES, stream, (u32)seed_arg, (u32)rounds,
-                     (const u32*)expected.data_ptr(), (u32*)l.res.data_ptr(),
-                     (int)max_records, l.dump, l.inj_wave, l.inj_round, l.inj_stage,
-                     l.inj_mask);
-  hipError_t launch_err = hipGetLastError();
-  (void)hipEventRecord(t1, stream);
-  hipError_t sync_err = hipEventSynchronize(t1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  C10_HIP_CHECK(launch_err);
-  C10_HIP_CHECK(sync_err);
-  return cu_read_result(l.res, max_records, (double)ms / 1e3);
+  return cu_launch_timed(fpcheck_kernel, l, MAX_LDS_BYTES, max_records, (u32)seed_arg,
+                         (u32)rounds, (const u32*)expected.data_ptr(),
+                         (u32*)l.res.data_ptr(), (int)max_records, l.dump, l.inj_wave,
+                         l.inj_round, l.inj_stage, l.inj_mask);
 }
 
 // The raw result bits of one stage and round as an int64 tensor on the
 // current GPU, [operations x slots].
 at::Tensor fpcheck_values(int64_t seed_arg, int64_t stage, int64_t round) {
-  TORCH_CHECK(seed_arg >= 0 && seed_arg <= 0xFFFFFFFFLL, "fpcheck: seed must be a u32");
-  TORCH_CHECK(stage >= 0 && stage < N_STAGES, "fpcheck: stage must be in 0..",
-              N_STAGES - 1, ", got ", stage);
-  TORCH_CHECK(round >= 0 && round < MAX_ROUNDS, "fpcheck: round must be in 0..",
-              MAX_ROUNDS - 1, ", got ", round);
+  cu_check_wave_args("fpcheck", seed_arg, stage, round);
   at::Tensor out = at::zeros({(int64_t)FP_OPS[stage] * FP_SLOTS[stage]},
                              at::TensorOptions().dtype(at::kLong).device(at::kCUDA));
   auto stream = at::hip::getCurrentHIPStream();

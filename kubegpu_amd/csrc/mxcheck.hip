@@ -179,22 +179,8 @@ mxcheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
                             4.f, lane);
     dig[3] = mx_fold_f64(mx_stage_f64(cu_base(seed, MX_STAGE0 + 3, r), lane), lane);
 
-    // test hook: one scalar compare per round
-    if (gwave == inj_wave && r == inj_round) {
-#pragma unroll
-      for (u32 st = 0; st < N_STAGES; ++st)
-        if (st == inj_stage) dig[st] ^= inj_mask;
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (u32 st = 0; st < N_STAGES; ++st) {
-        u32 want = expected[r * N_STAGES + st];
-        if (dig[st] != want)
-          log_mismatch(res, max_records, gwave, hw, r, st, want, dig[st]);
-        if (dump != nullptr)
-          dump[((size_t)gwave * rounds + r) * N_STAGES + st] = dig[st];
-      }
-    }
+    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
+                   inj_wave, inj_round, inj_stage, inj_mask);
   }
 #endif
 }
@@ -246,41 +232,16 @@ CucheckOut mxcheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
                           max_records, dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
 
-  // more than 64 KiB of dynamic LDS has to be asked for; the kernel
-  // never touches it, it only keeps a second workgroup off the CU
-  C10_HIP_CHECK(hipFuncSetAttribute((const void*)mxcheck_kernel,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    MAX_LDS_BYTES));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipEvent_t t0, t1;
-  C10_HIP_CHECK(hipEventCreate(&t0));
-  C10_HIP_CHECK(hipEventCreate(&t1));
-  C10_HIP_CHECK(hipEventRecord(t0, stream));
-  hipLaunchKernelGGL(mxcheck_kernel, dim3((unsigned)l.blocks), dim3(CU_BLOCK),
-                     (size_t)MAX_LDS_BYTES, stream, (u32)seed_arg, (u32)rounds,
-                     (const u32*)expected.data_ptr(), (u32*)l.res.data_ptr(),
-                     (int)max_records, l.dump, l.inj_wave, l.inj_round, l.inj_stage,
-                     l.inj_mask);
-  hipError_t launch_err = hipGetLastError();
-  (void)hipEventRecord(t1, stream);
-  hipError_t sync_err = hipEventSynchronize(t1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  C10_HIP_CHECK(launch_err);
-  C10_HIP_CHECK(sync_err);
-  return cu_read_result(l.res, max_records, (double)ms / 1e3);
+  return cu_launch_timed(mxcheck_kernel, l, MAX_LDS_BYTES, max_records, (u32)seed_arg,
+                         (u32)rounds, (const u32*)expected.data_ptr(),
+                         (u32*)l.res.data_ptr(), (int)max_records, l.dump, l.inj_wave,
+                         l.inj_round, l.inj_stage, l.inj_mask);
 }
 
 // The accumulator tile of one stage and round as a float64 tensor on the
 // current GPU, [32, 32] or [16, 16].
 at::Tensor mxcheck_tile(int64_t seed_arg, int64_t stage, int64_t round) {
-  TORCH_CHECK(seed_arg >= 0 && seed_arg <= 0xFFFFFFFFLL, "mxcheck: seed must be a u32");
-  TORCH_CHECK(stage >= 0 && stage < N_STAGES, "mxcheck: stage must be in 0..",
-              N_STAGES - 1, ", got ", stage);
-  TORCH_CHECK(round >= 0 && round < MAX_ROUNDS, "mxcheck: round must be in 0..",
-              MAX_ROUNDS - 1, ", got ", round);
+  cu_check_wave_args("mxcheck", seed_arg, stage, round);
   int64_t n = stage == 3 ? 16 : 32;
   at::Tensor out = at::zeros({n, n}, at::TensorOptions().dtype(at::kDouble).device(at::kCUDA));
   auto stream = at::hip::getCurrentHIPStream();

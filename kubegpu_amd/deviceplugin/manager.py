@@ -43,6 +43,7 @@ from ..discovery import (
     default_backend,
 )
 from ..plugintypes import RESOURCE_GPU
+from ..probe._active import ACTIVE_PROBES
 
 # Extracts the concrete GPU id out of a bound cards resource name
 # (cf. the reference's UUID regex at nvidia_gpu_manager.go:225).
@@ -88,9 +89,11 @@ class AMDGPUManager(Device):
         # allocatable 0) instead of silently shrinking the node, until
         # the grace window expires: uuid -> (last GpuInfo, swept-at).
         self.vanished: Dict[str, tuple] = {}
-        # Active HBM integrity (memcheck) verdicts: uuid -> verdict dict.
-        # Kept here, not on GpuInfo, because GpuInfo objects are replaced
-        # on every re-discovery and the verdict must outlive them.
+        # Verdicts of the active probes, one dict per name in
+        # ACTIVE_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
+        # because GpuInfo objects are replaced on every re-discovery and
+        # the verdict must outlive them.
+        # Active HBM integrity (memcheck) verdicts.
         self.memcheck: Dict[str, dict] = {}
         # Active compute-unit integrity (cucheck) verdicts, kept the same way.
         self.cucheck: Dict[str, dict] = {}
@@ -191,11 +194,8 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
-                    self.memcheck.pop(uuid, None)
-                    self.cucheck.pop(uuid, None)
-                    self.mxcheck.pop(uuid, None)
-                    self.fpcheck.pop(uuid, None)
-                    self.hostlink.pop(uuid, None)
+                    for probe in ACTIVE_PROBES:
+                        getattr(self, probe).pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
             self.bdf_to_id = {g.bdf: u for u, g in self.gpus.items() if g.bdf}
@@ -218,213 +218,127 @@ class AMDGPUManager(Device):
                 out.setdefault(u, False)
             return out
 
-    # -- active HBM integrity verdicts ---------------------------------------
+    # -- active probe verdicts ------------------------------------------------
 
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
-        """ECC health AND no failed memcheck, cucheck, mxcheck, fpcheck or
-        hostlink verdict (lock held)."""
-        m = self.memcheck.get(gpu.uuid)
-        c = self.cucheck.get(gpu.uuid)
-        x = self.mxcheck.get(gpu.uuid)
-        f = self.fpcheck.get(gpu.uuid)
-        h = self.hostlink.get(gpu.uuid)
-        return gpu.healthy and (m is None or m["ok"]) and (c is None or c["ok"]) \
-            and (x is None or x["ok"]) and (f is None or f["ok"]) \
-            and (h is None or h["ok"])
+        """ECC health AND no failed verdict of any active probe (lock
+        held)."""
+        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in ACTIVE_PROBES)
+        return gpu.healthy and all(v is None or v["ok"] for v in verdicts)
 
-    def record_memcheck(self, uuid: str, result: dict) -> bool:
-        """Store a memcheck result (MemcheckResult.to_dict()) for a GPU.
+    def _record(self, probe: str, uuid: str, result: dict, count_keys, describe) -> bool:
+        """Store a probe's result dict as the GPU's verdict.
 
-        A result with mismatched words marks the GPU unhealthy until a
-        later passing result or clear_memcheck(); returns the verdict's
-        ok flag.  Unknown uuids are rejected with KeyError."""
-        mismatched = int(result.get("mismatched_words", 0))
-        ok = bool(result.get("ok", mismatched == 0)) and mismatched == 0
-        verdict = dict(result)
-        verdict["ok"] = ok
-        verdict["mismatched_words"] = mismatched
-        verdict.setdefault("timestamp", time.time())
-        with self._lock:
-            if uuid not in self.gpus and uuid not in self.vanished:
-                raise KeyError(f"unknown GPU uuid {uuid}")
-            self.memcheck[uuid] = verdict
-        if not ok:
-            utils.errorf(
-                "memcheck FAILED on GPU %s: %d mismatched word(s), first bad "
-                "offset %s, bad bits 0x%08x — marking Unhealthy",
-                uuid, mismatched, verdict.get("first_bad_offset"),
-                int(verdict.get("bad_bits_mask") or 0),
-            )
-        return ok
-
-    def clear_memcheck(self, uuid: str) -> bool:
-        """Forget a GPU's verdict (operator override); True if one existed."""
-        with self._lock:
-            return self.memcheck.pop(uuid, None) is not None
-
-    def memcheck_status(self, uuid: str) -> Optional[dict]:
-        with self._lock:
-            v = self.memcheck.get(uuid)
-            return dict(v) if v is not None else None
-
-    # -- active compute-unit integrity verdicts ---------------------------------
-
-    def record_cucheck(self, uuid: str, result: dict) -> bool:
-        """Store a cucheck result (CucheckResult.to_dict()) for a GPU.
-
-        A result with mismatches marks the GPU unhealthy until a later
-        passing result or clear_cucheck(); returns the verdict's ok
-        flag.  Unknown uuids are rejected with KeyError."""
-        mismatches = int(result.get("mismatches", 0))
-        ok = bool(result.get("ok", mismatches == 0)) and mismatches == 0
-        verdict = dict(result)
-        verdict["ok"] = ok
-        verdict["mismatches"] = mismatches
-        verdict.setdefault("timestamp", time.time())
-        with self._lock:
-            if uuid not in self.gpus and uuid not in self.vanished:
-                raise KeyError(f"unknown GPU uuid {uuid}")
-            self.cucheck[uuid] = verdict
-        if not ok:
-            utils.errorf(
-                "cucheck FAILED on GPU %s: %d wrong digest(s), first bad round "
-                "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
-                uuid, mismatches, verdict.get("first_bad_round"),
-                ",".join(verdict.get("bad_stages") or []) or "?",
-                ",".join(verdict.get("bad_cus") or []) or "?",
-            )
-        return ok
-
-    def clear_cucheck(self, uuid: str) -> bool:
-        """Forget a GPU's verdict (operator override); True if one existed."""
-        with self._lock:
-            return self.cucheck.pop(uuid, None) is not None
-
-    def cucheck_status(self, uuid: str) -> Optional[dict]:
-        with self._lock:
-            v = self.cucheck.get(uuid)
-            return dict(v) if v is not None else None
-
-    # -- active matrix-core format integrity verdicts ----------------------------
-
-    def record_mxcheck(self, uuid: str, result: dict) -> bool:
-        """Store an mxcheck result (MxcheckResult.to_dict()) for a GPU.
-
-        A result with mismatches marks the GPU unhealthy until a later
-        passing result or clear_mxcheck(); returns the verdict's ok
-        flag.  Unknown uuids are rejected with KeyError."""
-        mismatches = int(result.get("mismatches", 0))
-        ok = bool(result.get("ok", mismatches == 0)) and mismatches == 0
-        verdict = dict(result)
-        verdict["ok"] = ok
-        verdict["mismatches"] = mismatches
-        verdict.setdefault("timestamp", time.time())
-        with self._lock:
-            if uuid not in self.gpus and uuid not in self.vanished:
-                raise KeyError(f"unknown GPU uuid {uuid}")
-            self.mxcheck[uuid] = verdict
-        if not ok:
-            utils.errorf(
-                "mxcheck FAILED on GPU %s: %d wrong digest(s), first bad round "
-                "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
-                uuid, mismatches, verdict.get("first_bad_round"),
-                ",".join(verdict.get("bad_stages") or []) or "?",
-                ",".join(verdict.get("bad_cus") or []) or "?",
-            )
-        return ok
-
-    def clear_mxcheck(self, uuid: str) -> bool:
-        """Forget a GPU's verdict (operator override); True if one existed."""
-        with self._lock:
-            return self.mxcheck.pop(uuid, None) is not None
-
-    def mxcheck_status(self, uuid: str) -> Optional[dict]:
-        with self._lock:
-            v = self.mxcheck.get(uuid)
-            return dict(v) if v is not None else None
-
-    # -- active IEEE rounding integrity verdicts -----------------------------------
-
-    def record_fpcheck(self, uuid: str, result: dict) -> bool:
-        """Store an fpcheck result (FpcheckResult.to_dict()) for a GPU.
-
-        A result with mismatches marks the GPU unhealthy until a later
-        passing result or clear_fpcheck(); returns the verdict's ok
-        flag.  Unknown uuids are rejected with KeyError."""
-        mismatches = int(result.get("mismatches", 0))
-        ok = bool(result.get("ok", mismatches == 0)) and mismatches == 0
-        verdict = dict(result)
-        verdict["ok"] = ok
-        verdict["mismatches"] = mismatches
-        verdict.setdefault("timestamp", time.time())
-        with self._lock:
-            if uuid not in self.gpus and uuid not in self.vanished:
-                raise KeyError(f"unknown GPU uuid {uuid}")
-            self.fpcheck[uuid] = verdict
-        if not ok:
-            utils.errorf(
-                "fpcheck FAILED on GPU %s: %d wrong digest(s), first bad round "
-                "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
-                uuid, mismatches, verdict.get("first_bad_round"),
-                ",".join(verdict.get("bad_stages") or []) or "?",
-                ",".join(verdict.get("bad_cus") or []) or "?",
-            )
-        return ok
-
-    def clear_fpcheck(self, uuid: str) -> bool:
-        """Forget a GPU's verdict (operator override); True if one existed."""
-        with self._lock:
-            return self.fpcheck.pop(uuid, None) is not None
-
-    def fpcheck_status(self, uuid: str) -> Optional[dict]:
-        with self._lock:
-            v = self.fpcheck.get(uuid)
-            return dict(v) if v is not None else None
-
-    # -- active host-link integrity verdicts -------------------------------------
-
-    def record_hostlink(self, uuid: str, result: dict) -> bool:
-        """Store a hostlink result (HostlinkResult.to_dict()) for a GPU.
-
-        A result with words that arrived wrong (found by the GPU or by
-        the CPU's sample) marks the GPU unhealthy until a later passing
-        result or clear_hostlink(); a bandwidth figure below the floor
-        (below_floor) does not.  Returns the verdict's ok flag.  Unknown
-        uuids are rejected with KeyError."""
-        mismatched = int(result.get("mismatched_words", 0))
-        sampled = int(result.get("cpu_sample_mismatches", 0))
-        bad = mismatched + sampled
+        ``count_keys`` name the counts of wrong data in the result; a
+        verdict is ok only if the result says so (or does not say) and
+        all of them are 0.  A failed verdict marks the GPU unhealthy
+        until a later passing result or ``_clear``, and is logged with
+        the ``utils.errorf`` arguments ``describe(verdict)`` returns.
+        Returns the verdict's ok flag.  Unknown uuids are rejected with
+        KeyError."""
+        counts = {k: int(result.get(k, 0)) for k in count_keys}
+        bad = sum(counts.values())
         ok = bool(result.get("ok", bad == 0)) and bad == 0
         verdict = dict(result)
         verdict["ok"] = ok
-        verdict["mismatched_words"] = mismatched
-        verdict["cpu_sample_mismatches"] = sampled
+        verdict.update(counts)
         verdict.setdefault("timestamp", time.time())
         with self._lock:
             if uuid not in self.gpus and uuid not in self.vanished:
                 raise KeyError(f"unknown GPU uuid {uuid}")
-            self.hostlink[uuid] = verdict
+            getattr(self, probe)[uuid] = verdict
         if not ok:
-            first = (verdict.get("records") or [{}])[0]
-            utils.errorf(
+            utils.errorf(*describe(verdict))
+        return ok
+
+    def _clear(self, probe: str, uuid: str) -> bool:
+        """Forget a GPU's verdict (operator override); True if one existed."""
+        with self._lock:
+            return getattr(self, probe).pop(uuid, None) is not None
+
+    def _status(self, probe: str, uuid: str) -> Optional[dict]:
+        with self._lock:
+            v = getattr(self, probe).get(uuid)
+            return dict(v) if v is not None else None
+
+    def _record_digests(self, probe: str, uuid: str, result: dict) -> bool:
+        """``_record`` for cucheck, mxcheck and fpcheck, whose results
+        (``DigestResult.to_dict()``) count ``mismatches``."""
+        return self._record(probe, uuid, result, ("mismatches",), lambda v: (
+            probe + " FAILED on GPU %s: %d wrong digest(s), first bad round "
+            "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
+            uuid, v["mismatches"], v.get("first_bad_round"),
+            ",".join(v.get("bad_stages") or []) or "?",
+            ",".join(v.get("bad_cus") or []) or "?",
+        ))
+
+    def record_memcheck(self, uuid: str, result: dict) -> bool:
+        """``_record`` for a memcheck result (MemcheckResult.to_dict()),
+        which counts ``mismatched_words``."""
+        return self._record("memcheck", uuid, result, ("mismatched_words",), lambda v: (
+            "memcheck FAILED on GPU %s: %d mismatched word(s), first bad "
+            "offset %s, bad bits 0x%08x — marking Unhealthy",
+            uuid, v["mismatched_words"], v.get("first_bad_offset"),
+            int(v.get("bad_bits_mask") or 0),
+        ))
+
+    def clear_memcheck(self, uuid: str) -> bool:
+        return self._clear("memcheck", uuid)
+
+    def memcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("memcheck", uuid)
+
+    def record_cucheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("cucheck", uuid, result)
+
+    def clear_cucheck(self, uuid: str) -> bool:
+        return self._clear("cucheck", uuid)
+
+    def cucheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("cucheck", uuid)
+
+    def record_mxcheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("mxcheck", uuid, result)
+
+    def clear_mxcheck(self, uuid: str) -> bool:
+        return self._clear("mxcheck", uuid)
+
+    def mxcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("mxcheck", uuid)
+
+    def record_fpcheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("fpcheck", uuid, result)
+
+    def clear_fpcheck(self, uuid: str) -> bool:
+        return self._clear("fpcheck", uuid)
+
+    def fpcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("fpcheck", uuid)
+
+    def record_hostlink(self, uuid: str, result: dict) -> bool:
+        """``_record`` for a hostlink result (HostlinkResult.to_dict()):
+        words that arrived wrong, found by the GPU or by the CPU's
+        sample, fail the verdict; a bandwidth figure below the floor
+        (below_floor) does not."""
+        def describe(v: dict) -> tuple:
+            first = (v.get("records") or [{}])[0]
+            return (
                 "hostlink FAILED on GPU %s: %d mismatched word(s) seen by the GPU, "
                 "%d by the CPU sample; first record in pass %s (%s), first bad "
                 "offset %s, bad bits 0x%08x — marking Unhealthy",
-                uuid, mismatched, sampled, first.get("pass", "?"),
-                first.get("path", "?"), verdict.get("first_bad_offset"),
-                int(verdict.get("bad_bits_mask") or 0),
+                uuid, v["mismatched_words"], v["cpu_sample_mismatches"],
+                first.get("pass", "?"), first.get("path", "?"),
+                v.get("first_bad_offset"), int(v.get("bad_bits_mask") or 0),
             )
-        return ok
+
+        return self._record("hostlink", uuid, result,
+                            ("mismatched_words", "cpu_sample_mismatches"), describe)
 
     def clear_hostlink(self, uuid: str) -> bool:
-        """Forget a GPU's verdict (operator override); True if one existed."""
-        with self._lock:
-            return self.hostlink.pop(uuid, None) is not None
+        return self._clear("hostlink", uuid)
 
     def hostlink_status(self, uuid: str) -> Optional[dict]:
-        with self._lock:
-            v = self.hostlink.get(uuid)
-            return dict(v) if v is not None else None
+        return self._status("hostlink", uuid)
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:

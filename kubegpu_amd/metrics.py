@@ -11,6 +11,8 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
+from .probe._active import ACTIVE_PROBES
+
 try:
     from prometheus_client import (
         CollectorRegistry,
@@ -25,6 +27,70 @@ except ImportError:  # pragma: no cover
     _HAVE_PROM = False
 
 
+# Per-GPU metrics of the active probes: probe -> rows of (attribute
+# suffix, "gauge" or "counter", metric suffix, help).  The attribute is
+# _<probe>_<suffix>, the metric kubegpu_amd_gpu_<probe>_<suffix>; all
+# are labelled by uuid and declared in this order.
+_PROBE_METRICS = {
+    "memcheck": (
+        ("words", "gauge", "mismatched_words",
+         "32-bit words that read back wrong in the last HBM memcheck"),
+        ("gbps", "gauge", "gbps", "throughput of the last HBM memcheck, GB/s"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed HBM memcheck"),
+        ("err", "counter", "errors_total",
+         "HBM memcheck runs that could not complete (not a memory fault)"),
+    ),
+    "cucheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last compute-unit cucheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last cucheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed compute-unit cucheck"),
+        ("err", "counter", "errors_total",
+         "cucheck runs that could not complete (not a compute fault)"),
+    ),
+    "mxcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last matrix-core format mxcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last mxcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed matrix-core format mxcheck"),
+        ("err", "counter", "errors_total",
+         "mxcheck runs that could not complete (not a matrix-core fault)"),
+    ),
+    "fpcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last IEEE rounding fpcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last fpcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed IEEE rounding fpcheck"),
+        ("err", "counter", "errors_total",
+         "fpcheck runs that could not complete (not a rounding fault)"),
+    ),
+    "hostlink": (
+        ("words", "gauge", "mismatches",
+         "32-bit words that crossed the host link wrong in the last hostlink"),
+        ("h2d", "gauge", "h2d_gbps",
+         "host-to-device bandwidth of GPU loads from pinned host memory "
+         "in the last hostlink, GB/s"),
+        ("d2h", "gauge", "d2h_gbps",
+         "device-to-host bandwidth of GPU stores to pinned host memory "
+         "in the last hostlink, GB/s"),
+        ("floor", "gauge", "below_floor",
+         "1 = a one-way figure of the last hostlink was under the "
+         "configured floor (health unaffected)"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed hostlink"),
+        ("err", "counter", "errors_total",
+         "hostlink runs that could not complete (not a link fault)"),
+    ),
+}
+
+
 class Metrics:
     def __init__(self, registry=None) -> None:
         self._lock = threading.Lock()
@@ -33,16 +99,11 @@ class Metrics:
         self.failures = 0
         self.gpu_health: Dict[str, bool] = {}
         self.gpu_in_use: Dict[str, bool] = {}
-        self.gpu_memcheck: Dict[str, dict] = {}
-        self.gpu_memcheck_errors: Dict[str, int] = {}
-        self.gpu_cucheck: Dict[str, dict] = {}
-        self.gpu_cucheck_errors: Dict[str, int] = {}
-        self.gpu_mxcheck: Dict[str, dict] = {}
-        self.gpu_mxcheck_errors: Dict[str, int] = {}
-        self.gpu_fpcheck: Dict[str, dict] = {}
-        self.gpu_fpcheck_errors: Dict[str, int] = {}
-        self.gpu_hostlink: Dict[str, dict] = {}
-        self.gpu_hostlink_errors: Dict[str, int] = {}
+        # gpu_<probe>: uuid -> what the last run's setter was given;
+        # gpu_<probe>_errors: uuid -> runs that could not complete
+        for probe in ACTIVE_PROBES:
+            setattr(self, f"gpu_{probe}", {})
+            setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
             # per-instance registry: multiple Metrics objects (tests,
             # embedded schedulers) must not collide in the global one
@@ -83,141 +144,12 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            self._memcheck_words = Gauge(
-                "kubegpu_amd_gpu_memcheck_mismatched_words",
-                "32-bit words that read back wrong in the last HBM memcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._memcheck_gbps = Gauge(
-                "kubegpu_amd_gpu_memcheck_gbps",
-                "throughput of the last HBM memcheck, GB/s",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._memcheck_ts = Gauge(
-                "kubegpu_amd_gpu_memcheck_last_run_timestamp_seconds",
-                "unix time of the last completed HBM memcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._memcheck_err = Counter(
-                "kubegpu_amd_gpu_memcheck_errors_total",
-                "HBM memcheck runs that could not complete (not a memory fault)",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._cucheck_mismatches = Gauge(
-                "kubegpu_amd_gpu_cucheck_mismatches",
-                "wave digests that came out wrong in the last compute-unit cucheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._cucheck_cus = Gauge(
-                "kubegpu_amd_gpu_cucheck_cus_covered",
-                "distinct compute units that ran a wave of the last cucheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._cucheck_ts = Gauge(
-                "kubegpu_amd_gpu_cucheck_last_run_timestamp_seconds",
-                "unix time of the last completed compute-unit cucheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._cucheck_err = Counter(
-                "kubegpu_amd_gpu_cucheck_errors_total",
-                "cucheck runs that could not complete (not a compute fault)",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._mxcheck_mismatches = Gauge(
-                "kubegpu_amd_gpu_mxcheck_mismatches",
-                "wave digests that came out wrong in the last matrix-core format mxcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._mxcheck_cus = Gauge(
-                "kubegpu_amd_gpu_mxcheck_cus_covered",
-                "distinct compute units that ran a wave of the last mxcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._mxcheck_ts = Gauge(
-                "kubegpu_amd_gpu_mxcheck_last_run_timestamp_seconds",
-                "unix time of the last completed matrix-core format mxcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._mxcheck_err = Counter(
-                "kubegpu_amd_gpu_mxcheck_errors_total",
-                "mxcheck runs that could not complete (not a matrix-core fault)",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._fpcheck_mismatches = Gauge(
-                "kubegpu_amd_gpu_fpcheck_mismatches",
-                "wave digests that came out wrong in the last IEEE rounding fpcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._fpcheck_cus = Gauge(
-                "kubegpu_amd_gpu_fpcheck_cus_covered",
-                "distinct compute units that ran a wave of the last fpcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._fpcheck_ts = Gauge(
-                "kubegpu_amd_gpu_fpcheck_last_run_timestamp_seconds",
-                "unix time of the last completed IEEE rounding fpcheck",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._fpcheck_err = Counter(
-                "kubegpu_amd_gpu_fpcheck_errors_total",
-                "fpcheck runs that could not complete (not a rounding fault)",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._hostlink_words = Gauge(
-                "kubegpu_amd_gpu_hostlink_mismatches",
-                "32-bit words that crossed the host link wrong in the last hostlink",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._hostlink_h2d = Gauge(
-                "kubegpu_amd_gpu_hostlink_h2d_gbps",
-                "host-to-device bandwidth of GPU loads from pinned host memory "
-                "in the last hostlink, GB/s",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._hostlink_d2h = Gauge(
-                "kubegpu_amd_gpu_hostlink_d2h_gbps",
-                "device-to-host bandwidth of GPU stores to pinned host memory "
-                "in the last hostlink, GB/s",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._hostlink_floor = Gauge(
-                "kubegpu_amd_gpu_hostlink_below_floor",
-                "1 = a one-way figure of the last hostlink was under the "
-                "configured floor (health unaffected)",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._hostlink_ts = Gauge(
-                "kubegpu_amd_gpu_hostlink_last_run_timestamp_seconds",
-                "unix time of the last completed hostlink",
-                ["uuid"],
-                registry=self.registry,
-            )
-            self._hostlink_err = Counter(
-                "kubegpu_amd_gpu_hostlink_errors_total",
-                "hostlink runs that could not complete (not a link fault)",
-                ["uuid"],
-                registry=self.registry,
-            )
+            for probe in ACTIVE_PROBES:
+                for attr, kind, name, help_text in _PROBE_METRICS[probe]:
+                    setattr(self, f"_{probe}_{attr}",
+                            (Gauge if kind == "gauge" else Counter)(
+                                f"kubegpu_amd_gpu_{probe}_{name}", help_text,
+                                ["uuid"], registry=self.registry))
 
     def observe_schedule(self, seconds: float) -> None:
         with self._lock:
@@ -254,104 +186,74 @@ class Metrics:
         if _HAVE_PROM:
             self._gpu_in_use.labels(uuid=uuid).set(1.0 if in_use else 0.0)
 
+    def _set_gpu_probe(self, probe: str, uuid: str, values: dict, timestamp: float) -> None:
+        """Export a completed run: ``values`` maps the key kept in
+        ``gpu_<probe>[uuid]`` to (value, attribute suffix of its gauge)."""
+        record = {key: v for key, (v, _) in values.items()}
+        record["timestamp"] = float(timestamp)
+        with self._lock:
+            getattr(self, f"gpu_{probe}")[uuid] = record
+        if _HAVE_PROM:
+            for v, attr in values.values():
+                getattr(self, f"_{probe}_{attr}").labels(uuid=uuid).set(float(v))
+            getattr(self, f"_{probe}_ts").labels(uuid=uuid).set(float(timestamp))
+
+    def _inc_probe_error(self, probe: str, uuid: str) -> None:
+        with self._lock:
+            errors = getattr(self, f"gpu_{probe}_errors")
+            errors[uuid] = errors.get(uuid, 0) + 1
+        if _HAVE_PROM:
+            getattr(self, f"_{probe}_err").labels(uuid=uuid).inc()
+
+    def _set_gpu_digests(self, probe: str, uuid: str, mismatches: int, cus_covered: int,
+                         timestamp: float) -> None:
+        self._set_gpu_probe(probe, uuid, {
+            "mismatches": (int(mismatches), "mismatches"),
+            "cus_covered": (int(cus_covered), "cus"),
+        }, timestamp)
+
     def set_gpu_memcheck(self, uuid: str, mismatched_words: int, gbps: float,
                          timestamp: float) -> None:
-        with self._lock:
-            self.gpu_memcheck[uuid] = {
-                "mismatched_words": int(mismatched_words),
-                "gbps": float(gbps),
-                "timestamp": float(timestamp),
-            }
-        if _HAVE_PROM:
-            self._memcheck_words.labels(uuid=uuid).set(float(mismatched_words))
-            self._memcheck_gbps.labels(uuid=uuid).set(float(gbps))
-            self._memcheck_ts.labels(uuid=uuid).set(float(timestamp))
+        self._set_gpu_probe("memcheck", uuid, {
+            "mismatched_words": (int(mismatched_words), "words"),
+            "gbps": (float(gbps), "gbps"),
+        }, timestamp)
 
     def inc_memcheck_error(self, uuid: str) -> None:
-        with self._lock:
-            self.gpu_memcheck_errors[uuid] = self.gpu_memcheck_errors.get(uuid, 0) + 1
-        if _HAVE_PROM:
-            self._memcheck_err.labels(uuid=uuid).inc()
+        self._inc_probe_error("memcheck", uuid)
 
     def set_gpu_cucheck(self, uuid: str, mismatches: int, cus_covered: int,
                         timestamp: float) -> None:
-        with self._lock:
-            self.gpu_cucheck[uuid] = {
-                "mismatches": int(mismatches),
-                "cus_covered": int(cus_covered),
-                "timestamp": float(timestamp),
-            }
-        if _HAVE_PROM:
-            self._cucheck_mismatches.labels(uuid=uuid).set(float(mismatches))
-            self._cucheck_cus.labels(uuid=uuid).set(float(cus_covered))
-            self._cucheck_ts.labels(uuid=uuid).set(float(timestamp))
+        self._set_gpu_digests("cucheck", uuid, mismatches, cus_covered, timestamp)
 
     def inc_cucheck_error(self, uuid: str) -> None:
-        with self._lock:
-            self.gpu_cucheck_errors[uuid] = self.gpu_cucheck_errors.get(uuid, 0) + 1
-        if _HAVE_PROM:
-            self._cucheck_err.labels(uuid=uuid).inc()
+        self._inc_probe_error("cucheck", uuid)
 
     def set_gpu_mxcheck(self, uuid: str, mismatches: int, cus_covered: int,
                         timestamp: float) -> None:
-        with self._lock:
-            self.gpu_mxcheck[uuid] = {
-                "mismatches": int(mismatches),
-                "cus_covered": int(cus_covered),
-                "timestamp": float(timestamp),
-            }
-        if _HAVE_PROM:
-            self._mxcheck_mismatches.labels(uuid=uuid).set(float(mismatches))
-            self._mxcheck_cus.labels(uuid=uuid).set(float(cus_covered))
-            self._mxcheck_ts.labels(uuid=uuid).set(float(timestamp))
+        self._set_gpu_digests("mxcheck", uuid, mismatches, cus_covered, timestamp)
 
     def inc_mxcheck_error(self, uuid: str) -> None:
-        with self._lock:
-            self.gpu_mxcheck_errors[uuid] = self.gpu_mxcheck_errors.get(uuid, 0) + 1
-        if _HAVE_PROM:
-            self._mxcheck_err.labels(uuid=uuid).inc()
+        self._inc_probe_error("mxcheck", uuid)
 
     def set_gpu_fpcheck(self, uuid: str, mismatches: int, cus_covered: int,
                         timestamp: float) -> None:
-        with self._lock:
-            self.gpu_fpcheck[uuid] = {
-                "mismatches": int(mismatches),
-                "cus_covered": int(cus_covered),
-                "timestamp": float(timestamp),
-            }
-        if _HAVE_PROM:
-            self._fpcheck_mismatches.labels(uuid=uuid).set(float(mismatches))
-            self._fpcheck_cus.labels(uuid=uuid).set(float(cus_covered))
-            self._fpcheck_ts.labels(uuid=uuid).set(float(timestamp))
+        self._set_gpu_digests("fpcheck", uuid, mismatches, cus_covered, timestamp)
 
     def inc_fpcheck_error(self, uuid: str) -> None:
-        with self._lock:
-            self.gpu_fpcheck_errors[uuid] = self.gpu_fpcheck_errors.get(uuid, 0) + 1
-        if _HAVE_PROM:
-            self._fpcheck_err.labels(uuid=uuid).inc()
+        self._inc_probe_error("fpcheck", uuid)
 
     def set_gpu_hostlink(self, uuid: str, mismatches: int, h2d_gbps: float,
                          d2h_gbps: float, below_floor: bool, timestamp: float) -> None:
-        with self._lock:
-            self.gpu_hostlink[uuid] = {
-                "mismatches": int(mismatches),
-                "h2d_gbps": float(h2d_gbps),
-                "d2h_gbps": float(d2h_gbps),
-                "below_floor": bool(below_floor),
-                "timestamp": float(timestamp),
-            }
-        if _HAVE_PROM:
-            self._hostlink_words.labels(uuid=uuid).set(float(mismatches))
-            self._hostlink_h2d.labels(uuid=uuid).set(float(h2d_gbps))
-            self._hostlink_d2h.labels(uuid=uuid).set(float(d2h_gbps))
-            self._hostlink_floor.labels(uuid=uuid).set(1.0 if below_floor else 0.0)
-            self._hostlink_ts.labels(uuid=uuid).set(float(timestamp))
+        self._set_gpu_probe("hostlink", uuid, {
+            "mismatches": (int(mismatches), "words"),
+            "h2d_gbps": (float(h2d_gbps), "h2d"),
+            "d2h_gbps": (float(d2h_gbps), "d2h"),
+            "below_floor": (bool(below_floor), "floor"),
+        }, timestamp)
 
     def inc_hostlink_error(self, uuid: str) -> None:
-        with self._lock:
-            self.gpu_hostlink_errors[uuid] = self.gpu_hostlink_errors.get(uuid, 0) + 1
-        if _HAVE_PROM:
-            self._hostlink_err.labels(uuid=uuid).inc()
+        self._inc_probe_error("hostlink", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

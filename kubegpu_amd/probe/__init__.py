@@ -83,25 +83,19 @@ _HOSTLINK_EXPORTS = (
 )
 
 
+_LAZY_EXPORTS = {
+    "memcheck": _MEMCHECK_EXPORTS,
+    "cucheck": _CUCHECK_EXPORTS,
+    "mxcheck": _MXCHECK_EXPORTS,
+    "fpcheck": _FPCHECK_EXPORTS,
+    "hostlink": _HOSTLINK_EXPORTS,
+}
+
+
 def __getattr__(name):
-    if name in _MEMCHECK_EXPORTS:
-        from . import memcheck as _memcheck
+    for module, names in _LAZY_EXPORTS.items():
+        if name in names:
+            import importlib
 
-        return getattr(_memcheck, name)
-    if name in _CUCHECK_EXPORTS:
-        from . import cucheck as _cucheck
-
-        return getattr(_cucheck, name)
-    if name in _MXCHECK_EXPORTS:
-        from . import mxcheck as _mxcheck
-
-        return getattr(_mxcheck, name)
-    if name in _FPCHECK_EXPORTS:
-        from . import fpcheck as _fpcheck
-
-        return getattr(_fpcheck, name)
-    if name in _HOSTLINK_EXPORTS:
-        from . import hostlink as _hostlink
-
-        return getattr(_hostlink, name)
+            return getattr(importlib.import_module(f"{__name__}.{module}"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

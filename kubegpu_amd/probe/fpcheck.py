@@ -120,27 +120,28 @@ CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
 
 from __future__ import annotations
 
-import json
-import os
-import subprocess
 import sys
-import time
-from dataclasses import dataclass, field
-from typing import Callable, Dict, List, Optional, Tuple
+from dataclasses import dataclass
+from typing import Callable, Dict, Optional, Tuple
 
-from .cucheck import (
-    WAVES_PER_BLOCK,
-    _base,
-    _fmix32,
-    _salt,
-)
-from .memcheck import (
+from . import _active
+from . import _digest as _shared  # _digest is this module's own fold
+from ._active import (  # noqa: F401
     EXIT_CANNOT_RUN,
     EXIT_MISMATCH,
     EXIT_PASS,
     _REPO_ROOT,
     _child_lock,
+    _ext,
     idle_gpus,
+)
+from ._digest import (  # noqa: F401
+    WAVES_PER_BLOCK,
+    DigestResult,
+    _base,
+    _device,
+    _fmix32,
+    _salt,
 )
 
 STAGES: Tuple[str, ...] = ("f32", "f64", "packed", "cvt")
@@ -710,21 +711,7 @@ def reference_digests(seed: int, rounds: int):
 # -- GPU run ---------------------------------------------------------------------
 
 @dataclass
-class FpcheckResult:
-    ok: bool = True
-    rounds: int = 0
-    waves: int = 0
-    mismatches: int = 0
-    first_bad_round: Optional[int] = None
-    bad_stages: List[str] = field(default_factory=list)
-    # {"wave", "block", "xcc", "se", "sh", "cu", "simd", "round", "stage",
-    #  "expected", "got"} per logged digest
-    records: List[Dict] = field(default_factory=list)
-    records_dropped: int = 0
-    cus_covered: int = 0  # distinct CUs that ran at least one wave
-    cu_count: int = 0  # multiProcessorCount
-    bad_cus: List[str] = field(default_factory=list)  # "xcc/se/sh/cu"
-    elapsed_s: float = 0.0
+class FpcheckResult(DigestResult):
     # Whole-run lower bounds per stage in 1e9 results per second (the
     # kernel's time also holds operand generation, the other stages and
     # the digests): informative.
@@ -732,70 +719,6 @@ class FpcheckResult:
     f64_gops: float = 0.0
     packed_gops: float = 0.0
     cvt_gops: float = 0.0
-    waves_on: List[int] = field(default_factory=list, repr=False)
-
-    def to_dict(self) -> dict:
-        return {
-            "ok": bool(self.ok),
-            "rounds": int(self.rounds),
-            "waves": int(self.waves),
-            "mismatches": int(self.mismatches),
-            "first_bad_round": self.first_bad_round,
-            "bad_stages": list(self.bad_stages),
-            "records": [dict(r) for r in self.records],
-            "records_dropped": int(self.records_dropped),
-            "cus_covered": int(self.cus_covered),
-            "cu_count": int(self.cu_count),
-            "bad_cus": list(self.bad_cus),
-            "elapsed_s": float(self.elapsed_s),
-            "f32_gops": float(self.f32_gops),
-            "f64_gops": float(self.f64_gops),
-            "packed_gops": float(self.packed_gops),
-            "cvt_gops": float(self.cvt_gops),
-        }
-
-
-def _ext():
-    from .bandwidth import load_ext
-
-    return load_ext(required=True)
-
-
-def _decode_record(raw) -> dict:
-    wave, hw, rnd, stage, expected, got = (int(x) for x in raw)
-    # hw = XCC_ID << 16 | HW_ID[15:0]; HW_ID: SIMD 5:4, CU 11:8, SH 12, SE 14:13
-    return {
-        "wave": wave,
-        "block": wave // WAVES_PER_BLOCK,
-        "xcc": (hw >> 16) & 0xF,
-        "se": (hw >> 13) & 0x3,
-        "sh": (hw >> 12) & 0x1,
-        "cu": (hw >> 8) & 0xF,
-        "simd": (hw >> 4) & 0x3,
-        "round": rnd,
-        "stage": STAGES[stage] if 0 <= stage < len(STAGES) else stage,
-        "expected": expected,
-        "got": got,
-    }
-
-
-def _device(device):
-    import torch
-
-    if device is None:
-        return torch.device("cuda", torch.cuda.current_device())
-    return torch.device(device)
-
-
-def _expected_tensor(table, rounds: int, device):
-    import numpy as np
-    import torch
-
-    table = np.array(table, dtype=np.uint32)  # own, writable copy for torch
-    if table.shape != (rounds, len(STAGES)):
-        raise ValueError(
-            f"fpcheck: expected table must be [{rounds}, {len(STAGES)}], got {table.shape}")
-    return torch.from_numpy(table.view(np.int32)).to(device)
 
 
 def fpcheck(
@@ -819,54 +742,25 @@ def fpcheck(
     one digest before the compare and ``_expected`` replaces the
     reference table; both are test hooks, since a test cannot corrupt a
     rounding unit."""
-    import torch
-
     rounds, blocks, seed = int(rounds), int(blocks), int(seed)
     ext = _ext()
     device = _device(device)
     if not 1 <= rounds <= 65536:
         raise ValueError(f"fpcheck: rounds must be in 1..65536, got {rounds}")
     table = _expected if _expected is not None else reference_digests(seed, rounds)
-    expected = _expected_tensor(table, rounds, device)
+    expected = _shared.expected_tensor("fpcheck", table, rounds, STAGES, device)
     inject = None if _inject is None else tuple(int(x) for x in _inject)
-    count, first, mask, records, waves_on, elapsed = ext.fpcheck_run(
-        expected, seed, rounds, blocks, int(max_records), None, inject)
-
-    res = FpcheckResult(rounds=rounds)
-    res.waves_on = [int(x) for x in waves_on]
-    res.waves = sum(res.waves_on)
-    res.mismatches = int(count)
-    res.ok = res.mismatches == 0
-    res.first_bad_round = int(first) if res.mismatches else None
-    res.bad_stages = [s for i, s in enumerate(STAGES) if (int(mask) >> i) & 1]
-    res.records = [_decode_record(r) for r in records]
-    res.records_dropped = res.mismatches - len(res.records)
-    res.cus_covered = sum(1 for x in res.waves_on if x)
-    res.cu_count = int(torch.cuda.get_device_properties(device).multi_processor_count)
-    res.bad_cus = sorted({f"{r['xcc']}/{r['se']}/{r['sh']}/{r['cu']}" for r in res.records})
-    res.elapsed_s = float(elapsed)
-    if res.elapsed_s > 0:
-        work = res.waves * rounds / res.elapsed_s / 1e9
-        (res.f32_gops, res.f64_gops, res.packed_gops,
-         res.cvt_gops) = (work * f for f in _OPS_PER_WAVE_ROUND)
-    return res
+    raw = ext.fpcheck_run(expected, seed, rounds, blocks, int(max_records), None, inject)
+    return _shared.fill_result(
+        FpcheckResult(rounds=rounds), raw, STAGES, device, _OPS_PER_WAVE_ROUND, 1e9)
 
 
 def wave_digests(seed: int, rounds: int, blocks: int = 0, device=None):
     """What every wave computed, as uint32[blocks*16, rounds, 4] — the
     same kernel as ``fpcheck`` with its dump pointer set."""
-    import numpy as np
-    import torch
-
-    rounds, blocks = int(rounds), int(blocks)
-    device = _device(device)
-    if blocks == 0:
-        blocks = int(torch.cuda.get_device_properties(device).multi_processor_count)
-    waves = blocks * WAVES_PER_BLOCK
-    expected = _expected_tensor(reference_digests(seed, rounds), rounds, device)
-    dump = torch.zeros(waves * rounds * len(STAGES), dtype=torch.int32, device=device)
-    _ext().fpcheck_run(expected, int(seed), rounds, blocks, 0, dump, None)
-    return dump.cpu().numpy().view(np.uint32).reshape(waves, rounds, len(STAGES))
+    return _shared.wave_digests(
+        "fpcheck", _ext().fpcheck_run, reference_digests(seed, rounds), STAGES,
+        seed, rounds, blocks, device)
 
 
 def wave_values(seed: int, stage: int, r: int, device=None):
@@ -888,98 +782,22 @@ def wave_values(seed: int, stage: int, r: int, device=None):
 
 def run_fpcheck_subprocess(index: int, rounds: int = DEFAULT_ROUNDS,
                            timeout_s: float = 120.0) -> dict:
-    """Run the fpcheck CLI for GPU ``index`` in a fresh child process
-    (never exec: the parent may hold the GPU open) and return its JSON
-    record with ``exit_code`` added.  Serialised on memcheck's child
-    lock, so the active probes never overlap on a GPU.  Raises
-    subprocess.TimeoutExpired when the child overruns (it is killed
-    first)."""
-    cmd = [sys.executable, "-m", "kubegpu_amd.probe.fpcheck",
-           "--device", str(int(index)), "--rounds", str(int(rounds))]
-    env = dict(os.environ)
-    env["PYTHONPATH"] = _REPO_ROOT + os.pathsep + env["PYTHONPATH"] \
-        if env.get("PYTHONPATH") else _REPO_ROOT
-    with _child_lock:
-        out = subprocess.run(cmd, capture_output=True, timeout=timeout_s,
-                             env=env, text=True)
-    lines = out.stdout.strip().splitlines()
-    try:
-        rec = json.loads(lines[-1])
-    except (IndexError, ValueError):
-        rec = {"error": f"no JSON from fpcheck child: {out.stderr[-500:]}"}
-        out.returncode = EXIT_CANNOT_RUN
-    rec["exit_code"] = out.returncode
-    return rec
+    """``_active.run_probe_subprocess`` for the fpcheck CLI."""
+    return _active.run_probe_subprocess("fpcheck", index, "--rounds", rounds, timeout_s)
 
 
 def fpcheck_round(manager, runner: Callable[[int, int], dict], metrics=None,
                   rounds: int = DEFAULT_ROUNDS,
                   max_process_count: Optional[int] = 0) -> Dict[str, dict]:
-    """Check every idle GPU once and record the verdicts.
-
-    Same selection as ``memcheck_round`` (no allocation, process_count
-    at most ``max_process_count``, None ignores it), in index order;
-    ``runner(index, rounds)`` is called and its result dict recorded on
-    the manager.  A runner that raises, times out or reports exit code
-    2 says nothing about the hardware: it is logged and counted as an
-    error, and the GPU's health is left as it was.  Returns
-    {uuid: result}."""
-    from ..api import utils
-
-    out: Dict[str, dict] = {}
-    for index, uuid in idle_gpus(manager, max_process_count):
-        try:
-            rec = runner(index, rounds)
-            if not isinstance(rec, dict):
-                raise TypeError(f"fpcheck runner returned {type(rec).__name__}")
-            if rec.get("exit_code") == EXIT_CANNOT_RUN or "mismatches" not in rec:
-                raise RuntimeError(rec.get("error") or "fpcheck could not run")
-        except Exception as e:  # not a rounding fault: health unchanged
-            utils.errorf("fpcheck on GPU %s (index %d) did not run: %s", uuid, index, e)
-            if metrics is not None:
-                metrics.inc_fpcheck_error(uuid)
-            out[uuid] = {"error": str(e), "exit_code": EXIT_CANNOT_RUN}
-            continue
-        try:
-            manager.record_fpcheck(uuid, rec)
-        except KeyError:  # vanished mid-round
-            continue
-        if metrics is not None:
-            metrics.set_gpu_fpcheck(
-                uuid, int(rec["mismatches"]), int(rec.get("cus_covered", 0)),
-                time.time(),
-            )
-        out[uuid] = rec
-    return out
+    """``_active.probe_round`` with ``runner(index, rounds)``."""
+    return _active.probe_round("fpcheck", "mismatches", _shared.metric_args, manager,
+                               runner, metrics, rounds, max_process_count)
 
 
 def main(argv=None) -> int:
-    import argparse
-
-    ap = argparse.ArgumentParser(prog="kubegpu-amd-fpcheck")
-    ap.add_argument("--device", type=int, required=True, metavar="INDEX")
-    ap.add_argument("--rounds", type=int, default=DEFAULT_ROUNDS, metavar="N")
-    ap.add_argument("--seed", type=int, default=0)
-    args = ap.parse_args(argv)
-
-    # pin before torch / HIP initialise (same as memcheck)
-    os.environ["ROCR_VISIBLE_DEVICES"] = str(args.device)
-    rec: dict
-    try:
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("no GPU visible")
-        torch.cuda.set_device(0)
-        result = fpcheck(seed=args.seed, rounds=args.rounds)
-        rec = result.to_dict()
-        code = EXIT_PASS if result.ok else EXIT_MISMATCH
-    except Exception as e:  # no GPU, extension missing, bad argument
-        rec = {"error": f"{type(e).__name__}: {e}"}
-        code = EXIT_CANNOT_RUN
-    rec["device"] = args.device
-    print(json.dumps(rec), flush=True)
-    return code
+    return _active.probe_main(
+        "fpcheck", "--rounds", DEFAULT_ROUNDS,
+        lambda args: fpcheck(seed=args.seed, rounds=args.rounds), argv)
 
 
 if __name__ == "__main__":

@@ -29,26 +29,28 @@ CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
 
 from __future__ import annotations
 
-import json
 import os
 import re
-import subprocess
 import sys
 import time
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional
 
-from .memcheck import (
+from . import _active
+from ._active import (  # noqa: F401
     EXIT_CANNOT_RUN,
     EXIT_MISMATCH,
     EXIT_PASS,
     _REPO_ROOT,
+    _child_lock,
+    _ext,
+    idle_gpus,
+)
+from .memcheck import (
     Pattern,
     VerifyResult,
-    _child_lock,
     _to_result,
     first_vector_arg,
-    idle_gpus,
     pattern_id,
     reference_words,
 )
@@ -65,12 +67,6 @@ _SAMPLE_EDGE_BYTES = 4096  # CPU-checked head and tail of pass 0
 _SAMPLE_VECTORS = 64  # plus this many vectors at seeded random positions
 _HOST_WRITE_CHUNK_VECTORS = 1 << 16  # 1 MiB of pattern per numpy batch
 _COPY_WARMUP_BYTES = 1 << 20  # untimed first copy each way
-
-
-def _ext():
-    from .bandwidth import load_ext
-
-    return load_ext(required=True)
 
 
 def _device_index(device) -> int:
@@ -440,120 +436,61 @@ def hostlink(
 
 def run_hostlink_subprocess(index: int, nbytes: int = DEFAULT_BYTES,
                             timeout_s: float = 120.0) -> dict:
-    """Run the hostlink CLI for GPU ``index`` in a fresh child process
-    (never exec: the parent may hold the GPU open) and return its JSON
-    record with ``exit_code`` added.  Serialised on memcheck's child
-    lock, so the three active probes never overlap.  Raises
-    subprocess.TimeoutExpired when the child overruns (it is killed
-    first)."""
-    cmd = [sys.executable, "-m", "kubegpu_amd.probe.hostlink",
-           "--device", str(int(index)), "--bytes", str(int(nbytes))]
-    env = dict(os.environ)
-    env["PYTHONPATH"] = _REPO_ROOT + os.pathsep + env["PYTHONPATH"] \
-        if env.get("PYTHONPATH") else _REPO_ROOT
-    with _child_lock:
-        out = subprocess.run(cmd, capture_output=True, timeout=timeout_s,
-                             env=env, text=True)
-    lines = out.stdout.strip().splitlines()
-    try:
-        rec = json.loads(lines[-1])
-    except (IndexError, ValueError):
-        rec = {"error": f"no JSON from hostlink child: {out.stderr[-500:]}"}
-        out.returncode = EXIT_CANNOT_RUN
-    rec["exit_code"] = out.returncode
-    return rec
+    """``_active.run_probe_subprocess`` for the hostlink CLI."""
+    return _active.run_probe_subprocess("hostlink", index, "--bytes", nbytes, timeout_s)
+
+
+def _attach_link(manager, min_gbps: float, uuid: str, rec: dict) -> None:
+    """Between the runner and ``record_hostlink``: attach the GPU's PCIe
+    link state (``read_pcie_link`` of its bdf, read here in the parent)
+    as ``link`` and apply ``min_gbps``.  A figure below the floor is
+    logged and exported and leaves health alone."""
+    from ..api import utils
+
+    gpu = manager.gpu_or_tombstone(uuid)
+    rec["link"] = read_pcie_link(gpu.bdf) if gpu is not None else None
+    rec["min_gbps"] = float(min_gbps)
+    rec["below_floor"] = _below_floor(rec, float(min_gbps))
+    if rec["below_floor"]:
+        utils.errorf(
+            "hostlink on GPU %s: below the %.1f GB/s floor (kernel h2d %.1f, "
+            "kernel d2h %.1f, copy h2d %.1f, copy d2h %.1f GB/s, link %s) — "
+            "health unchanged",
+            uuid, float(min_gbps), float(rec.get("kernel_h2d_gbps", 0.0)),
+            float(rec.get("kernel_d2h_gbps", 0.0)),
+            float(rec.get("copy_h2d_gbps", 0.0)),
+            float(rec.get("copy_d2h_gbps", 0.0)), rec["link"],
+        )
+
+
+def _metric_args(rec: dict) -> tuple:
+    return (
+        int(rec["mismatched_words"]) + int(rec.get("cpu_sample_mismatches", 0)),
+        float(rec.get("kernel_h2d_gbps", 0.0)),
+        float(rec.get("kernel_d2h_gbps", 0.0)),
+        bool(rec["below_floor"]),
+    )
 
 
 def hostlink_round(manager, runner: Callable[[int, int], dict], metrics=None,
                    nbytes: int = DEFAULT_BYTES,
                    max_process_count: Optional[int] = 0,
                    min_gbps: float = 0.0) -> Dict[str, dict]:
-    """Check every idle GPU once and record the verdicts.
-
-    Same selection as ``memcheck_round`` (no allocation, process_count
-    at most ``max_process_count``, None ignores it), in index order;
-    ``runner(index, nbytes)`` is called, the GPU's PCIe link state
-    (``read_pcie_link`` of its bdf, read here in the parent) is attached
-    as ``link`` and ``min_gbps`` is applied, and the result dict is
-    recorded on the manager.  A figure below the floor is logged and
-    exported and leaves health alone.  A runner that raises, times out
-    or reports exit code 2 says nothing about the link: it is logged
-    and counted as an error, and the GPU's health is left as it was.
-    Returns {uuid: result}."""
-    from ..api import utils
-
-    out: Dict[str, dict] = {}
-    for index, uuid in idle_gpus(manager, max_process_count):
-        try:
-            rec = runner(index, nbytes)
-            if not isinstance(rec, dict):
-                raise TypeError(f"hostlink runner returned {type(rec).__name__}")
-            if rec.get("exit_code") == EXIT_CANNOT_RUN or "mismatched_words" not in rec:
-                raise RuntimeError(rec.get("error") or "hostlink could not run")
-        except Exception as e:  # not a link fault: health unchanged
-            utils.errorf("hostlink on GPU %s (index %d) did not run: %s", uuid, index, e)
-            if metrics is not None:
-                metrics.inc_hostlink_error(uuid)
-            out[uuid] = {"error": str(e), "exit_code": EXIT_CANNOT_RUN}
-            continue
-        gpu = manager.gpu_or_tombstone(uuid)
-        rec["link"] = read_pcie_link(gpu.bdf) if gpu is not None else None
-        rec["min_gbps"] = float(min_gbps)
-        rec["below_floor"] = _below_floor(rec, float(min_gbps))
-        if rec["below_floor"]:
-            utils.errorf(
-                "hostlink on GPU %s: below the %.1f GB/s floor (kernel h2d %.1f, "
-                "kernel d2h %.1f, copy h2d %.1f, copy d2h %.1f GB/s, link %s) — "
-                "health unchanged",
-                uuid, float(min_gbps), float(rec.get("kernel_h2d_gbps", 0.0)),
-                float(rec.get("kernel_d2h_gbps", 0.0)),
-                float(rec.get("copy_h2d_gbps", 0.0)),
-                float(rec.get("copy_d2h_gbps", 0.0)), rec["link"],
-            )
-        try:
-            manager.record_hostlink(uuid, rec)
-        except KeyError:  # vanished mid-round
-            continue
-        if metrics is not None:
-            metrics.set_gpu_hostlink(
-                uuid,
-                int(rec["mismatched_words"]) + int(rec.get("cpu_sample_mismatches", 0)),
-                float(rec.get("kernel_h2d_gbps", 0.0)),
-                float(rec.get("kernel_d2h_gbps", 0.0)),
-                bool(rec["below_floor"]), time.time(),
-            )
-        out[uuid] = rec
-    return out
+    """``_active.probe_round`` with ``runner(index, nbytes)`` and
+    ``_attach_link`` before the result is recorded."""
+    return _active.probe_round(
+        "hostlink", "mismatched_words", _metric_args, manager, runner, metrics, nbytes,
+        max_process_count,
+        after_run=lambda uuid, rec: _attach_link(manager, min_gbps, uuid, rec))
 
 
 def main(argv=None) -> int:
-    import argparse
-
-    ap = argparse.ArgumentParser(prog="kubegpu-amd-hostlink")
-    ap.add_argument("--device", type=int, required=True, metavar="INDEX")
-    ap.add_argument("--bytes", type=int, default=DEFAULT_BYTES, metavar="N")
-    ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--min-gbps", type=float, default=0.0, metavar="X")
-    args = ap.parse_args(argv)
-
-    # pin before torch / HIP initialise (same as memcheck)
-    os.environ["ROCR_VISIBLE_DEVICES"] = str(args.device)
-    rec: dict
-    try:
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("no GPU visible")
-        torch.cuda.set_device(0)
-        result = hostlink(nbytes=args.bytes, seed=args.seed, min_gbps=args.min_gbps)
-        rec = result.to_dict()
-        code = EXIT_PASS if result.ok else EXIT_MISMATCH
-    except Exception as e:  # no GPU, extension missing, pinned allocation failed, bad size
-        rec = {"error": f"{type(e).__name__}: {e}"}
-        code = EXIT_CANNOT_RUN
-    rec["device"] = args.device
-    print(json.dumps(rec), flush=True)
-    return code
+    return _active.probe_main(
+        "hostlink", "--bytes", DEFAULT_BYTES,
+        lambda args: hostlink(nbytes=args.bytes, seed=args.seed, min_gbps=args.min_gbps),
+        argv,
+        add_arguments=lambda ap: ap.add_argument(
+            "--min-gbps", type=float, default=0.0, metavar="X"))
 
 
 if __name__ == "__main__":

@@ -27,14 +27,21 @@ CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
 
 from __future__ import annotations
 
-import json
-import os
-import subprocess
 import sys
-import threading
 import time
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Tuple, Union
+
+from . import _active
+from ._active import (  # noqa: F401
+    EXIT_CANNOT_RUN,
+    EXIT_MISMATCH,
+    EXIT_PASS,
+    _REPO_ROOT,
+    _child_lock,
+    _ext,
+    idle_gpus,
+)
 
 PATTERNS: Tuple[str, ...] = (
     "addr", "addr_inv", "checker", "checker_inv", "walk1", "walk0",
@@ -43,8 +50,6 @@ _ADDR_K = (0x00000000, 0x9E3779B9, 0x7F4A7C15, 0xF39CC060)
 # Infinity Cache size: a smaller buffer may be verified out of cache.
 LLC_BYTES = 256 << 20
 DEFAULT_BYTES = 1 << 30
-
-EXIT_PASS, EXIT_MISMATCH, EXIT_CANNOT_RUN = 0, 1, 2
 
 Pattern = Union[int, str]
 
@@ -125,12 +130,6 @@ def _to_result(raw) -> VerifyResult:
         bad_bits_mask=int(mask),
         records=[(int(w), int(e), int(g)) for (w, e, g) in records],
     )
-
-
-def _ext():
-    from .bandwidth import load_ext
-
-    return load_ext(required=True)
 
 
 def first_vector_arg(first_vector: int, name: str = "first_vector") -> int:
@@ -309,121 +308,28 @@ def memcheck(
 
 # -- child process -----------------------------------------------------------
 
-_REPO_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-_child_lock = threading.Lock()  # one active-probe child at a time (cucheck, hostlink too)
-
-
 def run_memcheck_subprocess(index: int, nbytes: int = DEFAULT_BYTES,
                             timeout_s: float = 120.0) -> dict:
-    """Run the memcheck CLI for GPU ``index`` in a fresh child process
-    (never exec: the parent may hold the GPU open) and return its JSON
-    record with ``exit_code`` added.  Raises subprocess.TimeoutExpired
-    when the child overruns (it is killed first)."""
-    cmd = [sys.executable, "-m", "kubegpu_amd.probe.memcheck",
-           "--device", str(int(index)), "--bytes", str(int(nbytes))]
-    env = dict(os.environ)
-    env["PYTHONPATH"] = _REPO_ROOT + os.pathsep + env["PYTHONPATH"] \
-        if env.get("PYTHONPATH") else _REPO_ROOT
-    with _child_lock:
-        out = subprocess.run(cmd, capture_output=True, timeout=timeout_s,
-                             env=env, text=True)
-    lines = out.stdout.strip().splitlines()
-    try:
-        rec = json.loads(lines[-1])
-    except (IndexError, ValueError):
-        rec = {"error": f"no JSON from memcheck child: {out.stderr[-500:]}"}
-        out.returncode = EXIT_CANNOT_RUN
-    rec["exit_code"] = out.returncode
-    return rec
+    """``_active.run_probe_subprocess`` for the memcheck CLI."""
+    return _active.run_probe_subprocess("memcheck", index, "--bytes", nbytes, timeout_s)
 
 
-def idle_gpus(manager, max_process_count: Optional[int]) -> List[Tuple[int, str]]:
-    """(index, uuid) of every present GPU an active probe may take, in
-    index order: no allocation, and process_count at most
-    max_process_count (None ignores process_count).  Shared with the
-    compute-unit probe (probe/cucheck.py) and the host-link probe
-    (probe/hostlink.py)."""
-    with manager._lock:
-        return sorted(
-            (g.index, u) for u, g in manager.gpus.items()
-            if not g.in_use and (
-                max_process_count is None or g.process_count <= max_process_count
-            )
-        )
+def _metric_args(rec: dict) -> tuple:
+    return int(rec["mismatched_words"]), float(rec.get("gbps", 0.0))
 
 
 def memcheck_round(manager, runner: Callable[[int, int], dict], metrics=None,
                    nbytes: int = DEFAULT_BYTES,
                    max_process_count: Optional[int] = 0) -> Dict[str, dict]:
-    """Check every idle GPU once and record the verdicts.
-
-    For each present GPU with no allocation (``in_use``) and no compute
-    process (``process_count``), in index order, ``runner(index,
-    nbytes)`` is called and its result dict recorded on the manager.
-    ``max_process_count`` is the highest process_count still taken as
-    idle: daemons that register on KFD make a node with no workload
-    report 1 or 2, so such nodes raise it to their resting value; None
-    ignores process_count altogether.  A
-    runner that raises, times out or reports exit code 2 says nothing
-    about the memory: it is logged and counted as an error, and the
-    GPU's health is left as it was.  Returns {uuid: result}."""
-    from ..api import utils
-
-    idle = idle_gpus(manager, max_process_count)
-    out: Dict[str, dict] = {}
-    for index, uuid in idle:
-        try:
-            rec = runner(index, nbytes)
-            if not isinstance(rec, dict):
-                raise TypeError(f"memcheck runner returned {type(rec).__name__}")
-            if rec.get("exit_code") == EXIT_CANNOT_RUN or "mismatched_words" not in rec:
-                raise RuntimeError(rec.get("error") or "memcheck could not run")
-        except Exception as e:  # not a memory fault: health unchanged
-            utils.errorf("memcheck on GPU %s (index %d) did not run: %s", uuid, index, e)
-            if metrics is not None:
-                metrics.inc_memcheck_error(uuid)
-            out[uuid] = {"error": str(e), "exit_code": EXIT_CANNOT_RUN}
-            continue
-        try:
-            manager.record_memcheck(uuid, rec)
-        except KeyError:  # vanished mid-round
-            continue
-        if metrics is not None:
-            metrics.set_gpu_memcheck(
-                uuid, int(rec["mismatched_words"]), float(rec.get("gbps", 0.0)),
-                time.time(),
-            )
-        out[uuid] = rec
-    return out
+    """``_active.probe_round`` with ``runner(index, nbytes)``."""
+    return _active.probe_round("memcheck", "mismatched_words", _metric_args, manager,
+                               runner, metrics, nbytes, max_process_count)
 
 
 def main(argv=None) -> int:
-    import argparse
-
-    ap = argparse.ArgumentParser(prog="kubegpu-amd-memcheck")
-    ap.add_argument("--device", type=int, required=True, metavar="INDEX")
-    ap.add_argument("--bytes", type=int, default=DEFAULT_BYTES, metavar="N")
-    ap.add_argument("--seed", type=int, default=0)
-    args = ap.parse_args(argv)
-
-    # pin before torch / HIP initialise (same as bench.py)
-    os.environ["ROCR_VISIBLE_DEVICES"] = str(args.device)
-    rec: dict
-    try:
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("no GPU visible")
-        torch.cuda.set_device(0)
-        result = memcheck(nbytes=args.bytes, seed=args.seed)
-        rec = result.to_dict()
-        code = EXIT_PASS if result.ok else EXIT_MISMATCH
-    except Exception as e:  # no GPU, extension missing, OOM, bad size
-        rec = {"error": f"{type(e).__name__}: {e}"}
-        code = EXIT_CANNOT_RUN
-    rec["device"] = args.device
-    print(json.dumps(rec), flush=True)
-    return code
+    return _active.probe_main(
+        "memcheck", "--bytes", DEFAULT_BYTES,
+        lambda args: memcheck(nbytes=args.bytes, seed=args.seed), argv)
 
 
 if __name__ == "__main__":

@@ -14,6 +14,7 @@ Usage:
 from __future__ import annotations
 
 import argparse
+import importlib
 import json
 import os
 import signal
@@ -24,6 +25,7 @@ from ..api import utils
 from ..deviceplugin import create_device_plugin
 from ..discovery import FakeBackend, default_backend, fixtures
 from ..metrics import METRICS
+from ..probe._active import ACTIVE_PROBES
 from . import dpapi
 from .kubelet_plugin import KubeletDevicePlugin
 
@@ -170,11 +172,8 @@ def main(argv=None) -> int:
         return 0
 
     watcher_started = False
-    next_memcheck = time.monotonic()  # first round on the first tick
-    next_cucheck = time.monotonic()
-    next_mxcheck = time.monotonic()
-    next_fpcheck = time.monotonic()
-    next_hostlink = time.monotonic()
+    # first round of every enabled probe on the first tick
+    next_due = {probe: time.monotonic() for probe in ACTIVE_PROBES}
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -222,83 +221,27 @@ def main(argv=None) -> int:
             reconcile_in_use(manager, client)
         except Exception as e:  # never let reconcile kill the agent
             utils.logf(2, "agent: pod-resources reconcile error: %s", e)
-        # active HBM integrity probe: one child process per idle GPU,
+        # active integrity probes: one child process per idle GPU,
         # after reconcile so in_use is current; a failed verdict flips
-        # device_health(), so wake ListAndWatch again afterwards
-        if args.memcheck_interval > 0 and time.monotonic() >= next_memcheck:
-            next_memcheck = time.monotonic() + args.memcheck_interval
+        # device_health(), so wake ListAndWatch again afterwards.  Their
+        # children share one lock, so no two overlap on a GPU.
+        for probe in ACTIVE_PROBES:
+            interval = getattr(args, f"{probe}_interval")
+            if not (interval > 0 and time.monotonic() >= next_due[probe]):
+                continue
+            next_due[probe] = time.monotonic() + interval
             try:
-                from ..probe.memcheck import memcheck_round, run_memcheck_subprocess
-
-                memcheck_round(manager, run_memcheck_subprocess, METRICS,
-                               args.memcheck_bytes,
-                               max_process_count=args.memcheck_max_procs)
+                mod = importlib.import_module(f"..probe.{probe}", __package__)
+                if probe in ("memcheck", "hostlink"):
+                    size = getattr(args, f"{probe}_bytes")
+                else:
+                    size = getattr(args, f"{probe}_rounds") or mod.DEFAULT_ROUNDS
+                extra = {"min_gbps": args.hostlink_min_gbps} if probe == "hostlink" else {}
+                getattr(mod, f"{probe}_round")(
+                    manager, getattr(mod, f"run_{probe}_subprocess"), METRICS, size,
+                    max_process_count=getattr(args, f"{probe}_max_procs"), **extra)
             except Exception as e:  # never let the probe kill the agent
-                utils.errorf("agent: memcheck round failed: %s", e)
-            plugin.servicer.notify()
-        # active compute-unit integrity probe, same shape; its children
-        # share memcheck's lock, so the two never overlap on a GPU
-        if args.cucheck_interval > 0 and time.monotonic() >= next_cucheck:
-            next_cucheck = time.monotonic() + args.cucheck_interval
-            try:
-                from ..probe.cucheck import (
-                    DEFAULT_ROUNDS,
-                    cucheck_round,
-                    run_cucheck_subprocess,
-                )
-
-                cucheck_round(manager, run_cucheck_subprocess, METRICS,
-                              args.cucheck_rounds or DEFAULT_ROUNDS,
-                              max_process_count=args.cucheck_max_procs)
-            except Exception as e:  # never let the probe kill the agent
-                utils.errorf("agent: cucheck round failed: %s", e)
-            plugin.servicer.notify()
-        # active matrix-core format integrity probe, same shape and the
-        # same lock
-        if args.mxcheck_interval > 0 and time.monotonic() >= next_mxcheck:
-            next_mxcheck = time.monotonic() + args.mxcheck_interval
-            try:
-                from ..probe.mxcheck import (
-                    DEFAULT_ROUNDS as MXCHECK_ROUNDS,
-                    mxcheck_round,
-                    run_mxcheck_subprocess,
-                )
-
-                mxcheck_round(manager, run_mxcheck_subprocess, METRICS,
-                              args.mxcheck_rounds or MXCHECK_ROUNDS,
-                              max_process_count=args.mxcheck_max_procs)
-            except Exception as e:  # never let the probe kill the agent
-                utils.errorf("agent: mxcheck round failed: %s", e)
-            plugin.servicer.notify()
-        # active IEEE rounding integrity probe, same shape and the same
-        # lock
-        if args.fpcheck_interval > 0 and time.monotonic() >= next_fpcheck:
-            next_fpcheck = time.monotonic() + args.fpcheck_interval
-            try:
-                from ..probe.fpcheck import (
-                    DEFAULT_ROUNDS as FPCHECK_ROUNDS,
-                    fpcheck_round,
-                    run_fpcheck_subprocess,
-                )
-
-                fpcheck_round(manager, run_fpcheck_subprocess, METRICS,
-                              args.fpcheck_rounds or FPCHECK_ROUNDS,
-                              max_process_count=args.fpcheck_max_procs)
-            except Exception as e:  # never let the probe kill the agent
-                utils.errorf("agent: fpcheck round failed: %s", e)
-            plugin.servicer.notify()
-        # active host-link integrity probe, same shape and the same lock
-        if args.hostlink_interval > 0 and time.monotonic() >= next_hostlink:
-            next_hostlink = time.monotonic() + args.hostlink_interval
-            try:
-                from ..probe.hostlink import hostlink_round, run_hostlink_subprocess
-
-                hostlink_round(manager, run_hostlink_subprocess, METRICS,
-                               args.hostlink_bytes,
-                               max_process_count=args.hostlink_max_procs,
-                               min_gbps=args.hostlink_min_gbps)
-            except Exception as e:  # never let the probe kill the agent
-                utils.errorf("agent: hostlink round failed: %s", e)
+                utils.errorf("agent: " + probe + " round failed: %s", e)
             plugin.servicer.notify()
         for uuid, ok in manager.device_health().items():
             g = manager.gpu_or_tombstone(uuid)
