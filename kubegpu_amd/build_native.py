@@ -8,11 +8,12 @@ Artifacts (all inside the package so they ship with the repo snapshot):
 * _ext/_gpuprobe*.so    — torch extension with CDNA4 bandwidth, HBM
                           integrity (memcheck), compute-unit integrity
                           (cucheck), matrix-core format integrity
-                          (mxcheck), IEEE rounding integrity (fpcheck)
-                          and host-link integrity (hostlink) kernels;
+                          (mxcheck), IEEE rounding integrity (fpcheck),
+                          atomic-unit integrity (atomcheck) and
+                          host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
-                          csrc/pattern_common.h, cucheck, mxcheck and
-                          fpcheck csrc/cucheck_common.h
+                          csrc/pattern_common.h, cucheck, mxcheck,
+                          fpcheck and atomcheck csrc/cucheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
 Rebuilds are skipped when the artifact is newer than its sources, the
@@ -92,12 +93,14 @@ def build_gpuprobe(verbose: bool = True) -> str:
     os.makedirs(EXT_DIR, exist_ok=True)
     # bandwidth kernels + HBM integrity (memcheck) kernels + compute-unit
     # integrity (cucheck) kernel + matrix-core format integrity (mxcheck)
-    # kernel + IEEE rounding integrity (fpcheck) kernel + host-link
-    # integrity (hostlink) kernels, one module; fpcheck.hip relies on -O3
-    # alone: no fast-math flag may be added here
+    # kernel + IEEE rounding integrity (fpcheck) kernel + atomic-unit
+    # integrity (atomcheck) kernel + host-link integrity (hostlink)
+    # kernels, one module; fpcheck.hip relies on -O3 alone: no fast-math
+    # flag may be added here
     srcs = [os.path.join(CSRC, name)
             for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip",
-                         "mxcheck.hip", "fpcheck.hip", "hostlink.hip")]
+                         "mxcheck.hip", "fpcheck.hip", "atomcheck.hip",
+                         "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
     deps = srcs + [os.path.join(CSRC, name)
                    for name in ("pattern_common.h", "cucheck_common.h")]

@@ -24,6 +24,9 @@ Modes:
   amddevs --hostlink      host-link (PCIe path) integrity and bandwidth
                           probe over the idle GPUs, same shape and exit
                           codes ([--bytes N])
+  amddevs --atomcheck     atomic-unit (LDS, L2 and memory-side atomics)
+                          integrity probe over the idle GPUs, same shape and
+                          exit codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -37,7 +40,7 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import ACTIVE_PROBES, EXIT_CANNOT_RUN
+from ..probe._active import EXIT_CANNOT_RUN, HEALTH_PROBES
 
 # probe -> (what the --fake backend lacks, size argument, name of its
 # default in the probe's module, result keys that count wrong data)
@@ -48,6 +51,8 @@ _PROBE_RUNS = {
     "fpcheck": ("FP units", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "hostlink": ("host link", "bytes", "DEFAULT_BYTES",
                  ("mismatched_words", "cpu_sample_mismatches")),
+    "atomcheck": ("atomic units", "rounds", "DEFAULT_ROUNDS",
+                  ("mismatches", "shared_mismatches")),
 }
 
 
@@ -105,7 +110,7 @@ def main(argv=None) -> int:
                    help="run the compute-unit integrity probe on every GPU "
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
-                   help="with --cucheck, --mxcheck or --fpcheck: rounds per GPU "
+                   help="with --cucheck, --mxcheck, --fpcheck or --atomcheck: rounds per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
@@ -118,6 +123,10 @@ def main(argv=None) -> int:
     p.add_argument("--hostlink", action="store_true",
                    help="run the host-link integrity and bandwidth probe on "
                         "every GPU this command can see no allocation on")
+    p.add_argument("--atomcheck", action="store_true",
+                   help="run the atomic-unit integrity probe (LDS, L2 and "
+                        "memory-side atomics) on every GPU this command can "
+                        "see no allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -148,7 +157,7 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    for probe in ACTIVE_PROBES:
+    for probe in HEALTH_PROBES:
         if getattr(args, probe):
             return _run_probe(probe, args, backend)
     if args.health:
@@ -167,6 +176,7 @@ def main(argv=None) -> int:
                 "process_count": g.process_count if g else None,
                 "mxcheck": mgr.mxcheck_status(uuid),
                 "fpcheck": mgr.fpcheck_status(uuid),
+                "atomcheck": mgr.atomcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

@@ -43,7 +43,7 @@ from ..discovery import (
     default_backend,
 )
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import ACTIVE_PROBES
+from ..probe._active import HEALTH_PROBES
 
 # Extracts the concrete GPU id out of a bound cards resource name
 # (cf. the reference's UUID regex at nvidia_gpu_manager.go:225).
@@ -90,7 +90,7 @@ class AMDGPUManager(Device):
         # the grace window expires: uuid -> (last GpuInfo, swept-at).
         self.vanished: Dict[str, tuple] = {}
         # Verdicts of the active probes, one dict per name in
-        # ACTIVE_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
+        # HEALTH_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
         # because GpuInfo objects are replaced on every re-discovery and
         # the verdict must outlive them.
         # Active HBM integrity (memcheck) verdicts.
@@ -103,6 +103,8 @@ class AMDGPUManager(Device):
         self.fpcheck: Dict[str, dict] = {}
         # Active host-link integrity (hostlink) verdicts, kept the same way.
         self.hostlink: Dict[str, dict] = {}
+        # Active atomic-unit integrity (atomcheck) verdicts, kept the same way.
+        self.atomcheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -194,7 +196,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
-                    for probe in ACTIVE_PROBES:
+                    for probe in HEALTH_PROBES:
                         getattr(self, probe).pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
@@ -208,7 +210,7 @@ class AMDGPUManager(Device):
 
         Present GPUs are healthy unless they report uncorrectable ECC
         errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
-        mxcheck, fpcheck or hostlink verdict;
+        mxcheck, fpcheck, hostlink or atomcheck verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -223,7 +225,7 @@ class AMDGPUManager(Device):
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
         """ECC health AND no failed verdict of any active probe (lock
         held)."""
-        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in ACTIVE_PROBES)
+        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in HEALTH_PROBES)
         return gpu.healthy and all(v is None or v["ok"] for v in verdicts)
 
     def _record(self, probe: str, uuid: str, result: dict, count_keys, describe) -> bool:
@@ -340,6 +342,26 @@ class AMDGPUManager(Device):
     def hostlink_status(self, uuid: str) -> Optional[dict]:
         return self._status("hostlink", uuid)
 
+    def record_atomcheck(self, uuid: str, result: dict) -> bool:
+        """``_record`` for an atomcheck result (AtomcheckResult.to_dict()):
+        wrong wave digests and wrong cells of the shared region both fail
+        the verdict."""
+        return self._record(
+            "atomcheck", uuid, result, ("mismatches", "shared_mismatches"), lambda v: (
+                "atomcheck FAILED on GPU %s: %d wrong digest(s), %d wrong shared "
+                "cell(s), first bad round %s, stages %s, CUs (xcc/se/sh/cu) %s — "
+                "marking Unhealthy",
+                uuid, v["mismatches"], v["shared_mismatches"], v.get("first_bad_round"),
+                ",".join(v.get("bad_stages") or []) or "?",
+                ",".join(v.get("bad_cus") or []) or "?",
+            ))
+
+    def clear_atomcheck(self, uuid: str) -> bool:
+        return self._clear("atomcheck", uuid)
+
+    def atomcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("atomcheck", uuid)
+
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:
             g = self.gpus.get(uuid)
@@ -415,8 +437,8 @@ class AMDGPUManager(Device):
             return
         with self._lock:
             # capacity counts every discovered GPU; allocatable excludes
-            # ECC-unhealthy, memcheck-failed, cucheck-failed, mxcheck-failed, fpcheck-failed
-            # and hostlink-failed ones (such a GPU stays visible but must not take new pods — mirrors the
+            # ECC-unhealthy, memcheck-failed, cucheck-failed, mxcheck-failed, fpcheck-failed,
+            # hostlink-failed and atomcheck-failed ones (such a GPU stays visible but must not take new pods — mirrors the
             # kubelet plugin's per-device Unhealthy advertisement)
             count = len(self.gpus)
             healthy_count = sum(1 for g in self.gpus.values() if self._gpu_healthy(g))

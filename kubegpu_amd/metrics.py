@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
-from .probe._active import ACTIVE_PROBES
+from .probe._active import HEALTH_PROBES
 
 try:
     from prometheus_client import (
@@ -88,6 +88,18 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "hostlink runs that could not complete (not a link fault)"),
     ),
+    "atomcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last atomic-unit atomcheck"),
+        ("shared", "gauge", "shared_mismatches",
+         "cells of the cross-workgroup region that came out wrong in the last atomcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last atomcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed atomic-unit atomcheck"),
+        ("err", "counter", "errors_total",
+         "atomcheck runs that could not complete (not an atomic-unit fault)"),
+    ),
 }
 
 
@@ -101,7 +113,7 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         # gpu_<probe>: uuid -> what the last run's setter was given;
         # gpu_<probe>_errors: uuid -> runs that could not complete
-        for probe in ACTIVE_PROBES:
+        for probe in HEALTH_PROBES:
             setattr(self, f"gpu_{probe}", {})
             setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
@@ -128,7 +140,7 @@ class Metrics:
             )
             self._gpu_health = Gauge(
                 "kubegpu_amd_gpu_healthy",
-                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck/hostlink/fpcheck/mxcheck)",
+                "1 = GPU healthy, 0 = unhealthy (ECC/vanished/memcheck/cucheck/hostlink/fpcheck/mxcheck)/atomcheck",
                 ["uuid"],
                 registry=self.registry,
             )
@@ -144,7 +156,7 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            for probe in ACTIVE_PROBES:
+            for probe in HEALTH_PROBES:
                 for attr, kind, name, help_text in _PROBE_METRICS[probe]:
                     setattr(self, f"_{probe}_{attr}",
                             (Gauge if kind == "gauge" else Counter)(
@@ -254,6 +266,17 @@ class Metrics:
 
     def inc_hostlink_error(self, uuid: str) -> None:
         self._inc_probe_error("hostlink", uuid)
+
+    def set_gpu_atomcheck(self, uuid: str, mismatches: int, shared_mismatches: int,
+                          cus_covered: int, timestamp: float) -> None:
+        self._set_gpu_probe("atomcheck", uuid, {
+            "mismatches": (int(mismatches), "mismatches"),
+            "shared_mismatches": (int(shared_mismatches), "shared"),
+            "cus_covered": (int(cus_covered), "cus"),
+        }, timestamp)
+
+    def inc_atomcheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("atomcheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

@@ -83,12 +83,25 @@ _HOSTLINK_EXPORTS = (
 )
 
 
+# Atomic-unit integrity probe (probe/atomcheck.py), the same way; the
+# atomcheck() function is `kubegpu_amd.probe.atomcheck.atomcheck`.  Its
+# reference_digests / wave_digests / wave_values stay in the submodule
+# too.
+_ATOMCHECK_EXPORTS = (
+    "AtomcheckResult",
+    "atomcheck_round",
+    "reference_shared",
+    "run_atomcheck_subprocess",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
     "mxcheck": _MXCHECK_EXPORTS,
     "fpcheck": _FPCHECK_EXPORTS,
     "hostlink": _HOSTLINK_EXPORTS,
+    "atomcheck": _ATOMCHECK_EXPORTS,
 }
 
 

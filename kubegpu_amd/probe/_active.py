@@ -1,5 +1,5 @@
-"""What the five active integrity probes (memcheck, cucheck, mxcheck,
-fpcheck, hostlink) share: the exit codes, the one child-process lock,
+"""What the active integrity probes (memcheck, cucheck, mxcheck,
+fpcheck, hostlink, atomcheck) share: the exit codes, the one child-process lock,
 the child runner, the round over a node's idle GPUs and the CLI body.
 Each probe module binds these to its own name, so a probe adds only
 what is its own: kernels, reference, result type.
@@ -20,11 +20,15 @@ from typing import Callable, Dict, List, Optional, Tuple
 # In the order the manager, the metrics, the agent and the CLI go
 # through them.
 ACTIVE_PROBES: Tuple[str, ...] = ("memcheck", "cucheck", "mxcheck", "fpcheck", "hostlink")
+# Every probe whose verdict decides a GPU's health: what the manager,
+# the metrics, the agent loop and the CLI iterate.  ACTIVE_PROBES stays
+# the first five; later probes are appended here.
+HEALTH_PROBES: Tuple[str, ...] = ACTIVE_PROBES + ("atomcheck",)
 
 EXIT_PASS, EXIT_MISMATCH, EXIT_CANNOT_RUN = 0, 1, 2
 
 _REPO_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-# One active-probe child at a time, whichever of the five probes it
+# One active-probe child at a time, whichever of the probes it
 # runs: two probes never overlap on a GPU, nor on the host's memory.
 _child_lock = threading.Lock()
 

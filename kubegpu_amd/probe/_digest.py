@@ -1,5 +1,5 @@
-"""What the three digest probes (cucheck, mxcheck, fpcheck) share on the
-host: the hash that generates their inputs, the result type, the
+"""What the digest probes (cucheck, mxcheck, fpcheck, atomcheck) share on
+the host: the hash that generates their inputs, the result type, the
 decoding of the kernel's result block and the dump run.  Their kernels
 share csrc/cucheck_common.h the same way.
 

@@ -41,7 +41,9 @@ so the reference is integer arithmetic — and rounding logic is therefore
 not covered: it is ``probe/fpcheck.py``'s ground.  The f16, fp8, MXFP4
 and f64 matrix paths are
 ``probe/mxcheck.py``'s ground; transcendental units are not covered,
-nor is the path to HBM (memcheck's ground).
+nor is the path to HBM (memcheck's ground).  The LDS stage uses plain
+reads and writes only: LDS, L2 and memory-side atomics are
+``probe/atomcheck.py``'s ground.
 
 CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
     python -m kubegpu_amd.probe.cucheck --device INDEX [--rounds N] [--seed S]

@@ -112,7 +112,8 @@ Not covered: standalone v_exp, v_log, v_sin and v_cos — IEEE does not
 define their results, so no independent exact reference exists; their
 unit is reached only through the v_rcp, v_rsq and v_sqrt seeds inside
 division and square root.  fp8 conversions.  Rounding modes other than
-nearest-even.
+nearest-even.  Atomic operations, float ones included: they execute in
+units of their own, which are ``probe/atomcheck.py``'s ground.
 
 CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
     python -m kubegpu_amd.probe.fpcheck --device INDEX [--rounds N] [--seed S]
