@@ -3,7 +3,8 @@
 // that run one 16-wave workgroup per compute unit; all three files
 // compile into _gpuprobe and add only their stages:
 //   cucheck.hip  i8 / bf16 matrix cores, VALU, LDS (the one kernel that
-//                uses its dynamic LDS, hence its lds_dwords argument)
+//                uses its dynamic LDS, hence its lds_dwords argument), and
+//                a single-wave launcher that returns a stage's values
 //   mxcheck.hip  f16 / fp8 / MXFP4 / f64 matrix cores, and a single-wave
 //                launcher that returns one accumulator tile
 //   fpcheck.hip  IEEE rounding of the vector FP units, and a single-wave
@@ -139,16 +140,22 @@ __device__ __forceinline__ void cu_check_round(
   }
 }
 
-// Fold of a 32x32 accumulator tile.  C/D map of the 32x32 MFMAs: lane l,
-// register g holds row (g&3) + 8*(g>>2) + 4*(l>>5), column l&31.
+// C/D map of the 32x32 MFMAs: lane l, register g holds row
+// (g&3) + 8*(g>>2) + 4*(l>>5), column l&31.  Row-major index of that
+// element; the fold and cucheck's element dump both go through it.
+__device__ __forceinline__ u32 cu_tile_index(int g, int lane) {
+  u32 col = lane & 31, half = lane >> 5;
+  u32 row = (g & 3) + 8 * (g >> 2) + 4 * half;
+  return 32 * row + col;
+}
+
+// Fold of a 32x32 accumulator tile.
 template <typename ACC>
 __device__ __forceinline__ u32 fold_tile(const ACC& acc, int lane) {
-  u32 col = lane & 31, half = lane >> 5, d = 0;
+  u32 d = 0;
 #pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    u32 row = (g & 3) + 8 * (g >> 2) + 4 * half;
-    d += cu_fmix32((u32)(int)acc[g] + cu_salt(32 * row + col));
-  }
+  for (int g = 0; g < 16; ++g)
+    d += cu_fmix32((u32)(int)acc[g] + cu_salt(cu_tile_index(g, lane)));
   return wave_sum(d);
 }
 
@@ -283,8 +290,8 @@ static inline CucheckOut cu_launch_timed(Kernel kernel, const CuLaunch& l,
   return cu_read_result(l.res, max_records, (double)ms / 1e3);
 }
 
-// Argument checks of the single-wave launchers (mxcheck_tile,
-// fpcheck_values).
+// Argument checks of the single-wave launchers (cucheck_values,
+// mxcheck_tile, fpcheck_values).
 static inline void cu_check_wave_args(const char* who, int64_t seed_arg, int64_t stage,
                                       int64_t round) {
   TORCH_CHECK(seed_arg >= 0 && seed_arg <= 0xFFFFFFFFLL, who, ": seed must be a u32");

@@ -45,6 +45,26 @@ nor is the path to HBM (memcheck's ground).  The LDS stage uses plain
 reads and writes only: LDS, L2 and memory-side atomics are
 ``probe/atomcheck.py``'s ground.
 
+A digest says that something in a stage is wrong, not what.  Three
+functions give the values the digests are folded from, for one wave,
+stage and round:
+
+  wave_values(seed, stage, r, lds_bytes, wave)   what the GPU computed: the
+                    kernel's own stage code with a sink that stores
+                    instead of folding, run by one wave of one workgroup
+  reference_values(seed, stage, r, lds_dwords)   the same in numpy
+  fold_values(stage, values)                     the digest of either
+
+Value layouts, the same for both:
+
+  0, 1  int64[32, 32]          C[i][j] as above, read out of the
+                               accumulator registers through the C/D map
+                               the fold uses
+  2     uint32[32, 64]         [it, l] = x of lane l after iteration it;
+                               the digest folds the last row only
+  3     uint32[2, lds_dwords]  [p, d] = the word read back from dword d
+                               of the wave's slice in pass p: v[d], ~v[d]
+
 CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
     python -m kubegpu_amd.probe.cucheck --device INDEX [--rounds N] [--seed S]
 """
@@ -90,6 +110,8 @@ DEFAULT_ROUNDS = 22528
 _I8_OPS_PER_WAVE_ROUND = 2 * 32 * 32 * 256
 _BF16_FLOPS_PER_WAVE_ROUND = 2 * 32 * 32 * 128
 _REF_CHUNK = 128  # rounds per numpy batch
+# (rows, cols) of a stage's values; 0 stands for lds_dwords
+_VALUE_SHAPES = ((32, 32), (32, 32), (32, 64), (2, 0))
 
 
 # -- numpy definition ----------------------------------------------------------
@@ -184,6 +206,71 @@ def reference_digests(seed: int, rounds: int, lds_dwords: int = 2560):
     return out
 
 
+def _check_stage(who: str, stage: int) -> int:
+    stage = int(stage)
+    if stage not in range(len(STAGES)):
+        raise ValueError(f"{who}: stage must be in 0..3, got {stage}")
+    return stage
+
+
+def reference_values(seed: int, stage: int, r: int, lds_dwords: int = 2560):
+    """The values one wave's digest of ``stage`` in round ``r`` is folded
+    from, in the layouts of the module docstring.  Pure numpy."""
+    import numpy as np
+
+    stage = _check_stage("reference_values", stage)
+    seed, r, lds_dwords = int(seed) & 0xFFFFFFFF, int(r), int(lds_dwords)
+    if not 0 <= r < 65536 or lds_dwords <= 0:
+        raise ValueError("reference_values: r in 0..65535 and lds_dwords > 0 required")
+    if stage in (0, 1):
+        return matmul_tile(seed, stage, r)
+    rr = np.array([r], dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        if stage == 3:
+            v = _words(seed, 3, rr, 0, lds_dwords)[0]
+            return np.stack([v, ~v])
+        x = _words(seed, 2, rr, 0, 64)[0]
+        trace = np.empty((32, 64), dtype=np.uint32)
+        for it in range(32):
+            x = x * np.uint32(0x9E3779B1) + ((x << np.uint32(13)) | (x >> np.uint32(19)))
+            x = x ^ ((x.astype(np.uint64) * np.uint64(0x85EBCA6B))
+                     >> np.uint64(32)).astype(np.uint32)
+            # a*b + c < 2**24: the f32 FMA is exact, so integers define it
+            x = x + (x & np.uint32(0xFFF)) * ((x >> np.uint32(12)) & np.uint32(0xFFF)) \
+                + (x >> np.uint32(24))
+            trace[it] = x
+    return trace
+
+
+def fold_values(stage: int, values):
+    """The uint32 digest of one wave's values (``wave_values`` or
+    ``reference_values``), by the module docstring's definition.  Leading
+    axes are kept: values[..., rows, cols] gives digests[...]."""
+    import numpy as np
+
+    stage = _check_stage("fold_values", stage)
+    values = np.asarray(values)
+    rows, cols = _VALUE_SHAPES[stage]
+    if values.ndim >= 2 and cols == 0:
+        cols = values.shape[-1]  # lds_dwords
+    if values.ndim < 2 or values.shape[-2:] != (rows, cols) or cols == 0:
+        raise ValueError(f"fold_values: stage {stage} takes [..., {rows}, "
+                         f"{cols or 'lds_dwords'}], got {values.shape}")
+    lead = values.shape[:-2]
+    with np.errstate(over="ignore"):
+        if stage in (0, 1):
+            cu = (values.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+            salt = _salt(np.arange(1024, dtype=np.uint32))  # 32*i + j, row-major
+            h = _fmix32(cu.reshape(lead + (1024,)) + salt)
+        elif stage == 2:
+            h = _fmix32(values[..., -1, :].astype(np.uint32)
+                        + np.arange(64, dtype=np.uint32))
+        else:
+            salt = _salt(np.arange(cols, dtype=np.uint32))
+            h = _fmix32(values.astype(np.uint32) + salt).reshape(lead + (2 * cols,))
+        return h.sum(axis=-1, dtype=np.uint32)
+
+
 # -- GPU run ---------------------------------------------------------------------
 
 @dataclass
@@ -248,6 +335,26 @@ def wave_digests(seed: int, rounds: int, blocks: int = 0,
     return _digest.wave_digests(
         "cucheck", _ext().cucheck_run, reference_digests(seed, rounds, lds_bytes // 64),
         STAGES, seed, rounds, blocks, device, lds_bytes)
+
+
+def wave_values(seed: int, stage: int, r: int, lds_bytes: int = DEFAULT_LDS_BYTES,
+                wave: int = 0, device=None):
+    """What wave ``wave`` (0..15) of one workgroup with ``lds_bytes`` of
+    LDS computed for a stage and round, shaped like ``reference_values``:
+    the production kernel's stage code storing every value instead of
+    folding it.  A digest cannot say which element is wrong; this can."""
+    import numpy as np
+    import torch
+
+    stage = _check_stage("wave_values", stage)
+    with torch.cuda.device(_device(device)):
+        raw = _ext().cucheck_values(
+            int(seed), stage, int(r), int(lds_bytes), int(wave)).cpu().numpy()
+    if stage in (0, 1):
+        return raw
+    if (raw >> 32).any():
+        raise RuntimeError(f"cucheck: stage {stage} dump holds more than 32 bits")
+    return raw.astype(np.uint32)
 
 
 # -- child process -----------------------------------------------------------

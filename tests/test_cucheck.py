@@ -129,6 +129,89 @@ def test_lds_dwords_changes_only_the_lds_column():
     assert all(a[r, 3] != b[r, 3] for r in range(3))
 
 
+# -- reference_values and fold_values ---------------------------------------------
+
+TRIPLES = ((0, 0, 64), (0xDEADBEEF, 3, 64), (7, 130, 128))
+
+
+def test_fold_of_reference_values_is_the_reference_digest():
+    for seed, r, n in TRIPLES:
+        want = reference_digests(seed, r + 1, lds_dwords=n)[r]
+        for stage in range(4):
+            got = cc.fold_values(stage, cc.reference_values(seed, stage, r, n))
+            assert got.dtype == np.uint32 and got.shape == ()
+            assert int(got) == int(want[stage]), (seed, r, stage)
+
+
+def test_valu_trace_agrees_with_plain_integers():
+    M = 0xFFFFFFFF
+    for seed, r, _ in TRIPLES + ((0xFFFFFFFF, 65535, 64),):
+        trace = cc.reference_values(seed, 2, r)
+        base = _fmix(seed ^ ((3 * 0x9E3779B9) & M) ^ ((r * 0x7F4A7C15) & M))
+        for lane in (0, 63):
+            x = _fmix((base + lane) & M)
+            for it in range(32):
+                x = (x * 0x9E3779B1 + (((x << 13) | (x >> 19)) & M)) & M
+                x ^= (x * 0x85EBCA6B) >> 32
+                x = (x + (x & 0xFFF) * ((x >> 12) & 0xFFF) + (x >> 24)) & M
+                assert int(trace[it, lane]) == x, (seed, r, lane, it)
+        # The FMA's operands are those of x before the last line of an
+        # iteration, which the trace does not hold; redo the first two lines
+        # from the row above (the start words for iteration 0).
+        before = np.vstack([cc._words(seed, 2, np.array([r], dtype=np.uint32), 0, 64),
+                            trace[:-1]]).astype(np.uint64)
+        y = (before * 0x9E3779B1 + (((before << 13) | (before >> 19)) & M)) & M
+        y ^= (y * 0x85EBCA6B) >> 32
+        fma = (y & 0xFFF) * ((y >> 12) & 0xFFF) + (y >> 24)
+        assert int(fma.max()) <= 4095 * 4095 + 255 < 2 ** 24  # exact in f32
+        assert np.array_equal((y + fma) & M, trace)
+
+
+@pytest.mark.parametrize("stage", range(4))
+def test_fold_notices_any_single_bit_in_any_element(stage):
+    """fmix32 is a bijection, so one flipped bit in one folded element
+    changes that element's term and with it the sum — always."""
+    ref = cc.reference_values(0xDEADBEEF, stage, 1, 64)
+    clean = cc.fold_values(stage, ref)
+    rows, cols = ref.shape
+    lo = rows - 1 if stage == 2 else 0  # the valu digest folds the last row
+    n = (rows - lo) * cols
+    i, j = np.divmod(np.arange(n), cols)
+    for bit in range(32):
+        faulty = np.broadcast_to(ref, (n, rows, cols)).copy()
+        faulty[np.arange(n), lo + i, j] ^= ref.dtype.type(1 << bit)
+        got = cc.fold_values(stage, faulty)
+        assert got.shape == (n,)
+        assert (got != clean).all(), (bit, np.argwhere(got == clean)[:4].tolist())
+    if stage == 2:  # and only the last row
+        ref[:-1] ^= np.uint32(1)
+        assert cc.fold_values(2, ref) == clean
+
+
+def test_value_shapes_dtypes_and_bad_stage():
+    for stage, shape, dtype in ((0, (32, 32), np.int64), (1, (32, 32), np.int64),
+                                (2, (32, 64), np.uint32), (3, (2, 2560), np.uint32)):
+        v = cc.reference_values(5, stage, 2)
+        assert v.shape == shape and v.dtype == dtype, stage
+    v = cc.reference_values(5, 3, 2, 64)
+    assert v.shape == (2, 64) and np.array_equal(v[1], ~v[0])
+    assert np.array_equal(cc.reference_values(5, 0, 2), cc.matmul_tile(5, 0, 2))
+    for stage in (-1, 4):
+        with pytest.raises(ValueError):
+            cc.reference_values(0, stage, 0)
+        with pytest.raises(ValueError):
+            cc.fold_values(stage, np.zeros((32, 32), dtype=np.int64))
+        with pytest.raises(ValueError):
+            cc.wave_values(0, stage, 0)  # refused before the extension is loaded
+    for bad_r in (-1, 65536):
+        with pytest.raises(ValueError):
+            cc.reference_values(0, 2, bad_r)
+    with pytest.raises(ValueError):
+        cc.fold_values(2, np.zeros((32, 32), dtype=np.uint32))
+    with pytest.raises(ValueError):
+        cc.fold_values(3, np.zeros((64,), dtype=np.uint32))
+
+
 def test_lazy_reexports():
     from kubegpu_amd import probe
 

@@ -1,7 +1,10 @@
-"""Compute-unit integrity kernel on a real MI355X: every wave's digests
-against the numpy reference (which proves the MFMA lane maps), clean-run
-accounting, exact attribution of an injected fault, a tampered table,
-argument checks, the child process and CLI."""
+"""Compute-unit integrity kernel on a real MI355X: the values of every
+stage element by element against the exact numpy reference (the tile test
+proves the MFMA operand and C/D lane maps, the LDS test that every wave
+reads its own dwords at its own offsets), those values tied to the
+digests the production kernel compares, every wave's digests against the
+numpy reference, clean-run accounting, exact attribution of an injected
+fault, a tampered table, argument checks, the child process and CLI."""
 
 import functools
 import json
@@ -42,6 +45,90 @@ def ext():
 
 def expected_on_gpu(seed, rounds, lds_bytes=FULL_LDS):
     return torch.from_numpy(ref(seed, rounds, lds_bytes).view(np.int32).copy()).cuda()
+
+
+# 0. one wave's values, element by element ------------------------------------------
+
+# the last case is the top of both u32 ranges, where r * 0x7F4A7C15 wraps
+CASES = [(0, 0), (0xDEADBEEF, 1), (0xFFFFFFFF, 65535)]
+
+
+@pytest.mark.parametrize("seed,r", CASES)
+@pytest.mark.parametrize("stage", [0, 1])
+def test_wave_tile_equals_the_exact_product(stage, seed, r):
+    got = cc.wave_values(seed, stage, r)
+    want = cc.matmul_tile(seed, stage, r)
+    assert got.dtype == np.int64 and got.shape == want.shape == (32, 32)
+    bad = got != want
+    if bad.any():
+        i, j = (int(x) for x in np.argwhere(bad)[0])
+        halves_swapped = got.reshape(4, 2, 4, 32)[:, ::-1].reshape(32, 32)
+        pytest.fail(
+            f"stage {cc.STAGES[stage]}: first wrong element at (row {i}, col {j}): "
+            f"got {int(got[i, j])}, want {int(want[i, j])}; "
+            f"{int(bad.sum())} of {bad.size} differ, wrong per row "
+            f"{bad.sum(axis=1).tolist()}, per col {bad.sum(axis=0).tolist()}; "
+            f"transposed tile matches: {bool(np.array_equal(got.T, want))}; "
+            f"with the two half-waves' row blocks swapped it matches: "
+            f"{bool(np.array_equal(halves_swapped, want))}")
+
+
+@pytest.mark.parametrize("seed,r", CASES)
+def test_wave_valu_trace_equals_the_reference(seed, r):
+    got = cc.wave_values(seed, 2, r)
+    want = cc.reference_values(seed, 2, r)
+    assert got.dtype == np.uint32 and got.shape == want.shape == (32, 64)
+    bad = got != want
+    if bad.any():
+        it, lane = (int(x) for x in np.argwhere(bad)[0])
+        if it:
+            before = f"{int(got[it - 1, lane]):08x}"
+        else:  # the dump begins after iteration 0
+            start = cc._words(seed, 2, np.array([r], dtype=np.uint32), lane, 1)
+            before = f"the start word, not dumped (reference {int(start[0, 0]):08x})"
+        pytest.fail(
+            f"first wrong x after iteration {it} in lane {lane}: the GPU's x before "
+            f"that iteration was {before}; got {int(got[it, lane]):08x}, want "
+            f"{int(want[it, lane]):08x}; {int(bad.sum())} of {bad.size} differ, "
+            f"lanes wrong after the last iteration: {np.flatnonzero(bad[-1]).tolist()}")
+
+
+@pytest.mark.parametrize("lds_bytes,wave", [
+    (4096, 0), (4096, 7), (4096, 15), (FULL_LDS, 0),
+    (FULL_LDS, 15),  # this slice ends at the last byte of the CU's LDS
+])
+def test_wave_lds_readback_equals_the_reference(lds_bytes, wave):
+    n = lds_bytes // 64
+    for seed, r in CASES:
+        got = cc.wave_values(seed, 3, r, lds_bytes, wave)
+        want = cc.reference_values(seed, 3, r, n)
+        assert got.dtype == np.uint32 and got.shape == want.shape == (2, n)
+        bad = got != want
+        if bad.any():
+            p, d = (int(x) for x in np.argwhere(bad)[0])
+            pytest.fail(
+                f"seed {seed:#x} round {r}, wave {wave} of a {lds_bytes}-byte workgroup: "
+                f"first wrong word in pass {p} at dword {d} of the slice: got "
+                f"{int(got[p, d]):08x}, want {int(want[p, d]):08x}, xor "
+                f"{int(got[p, d] ^ want[p, d]):08x}; wrong per pass "
+                f"{bad.sum(axis=1).tolist()} of {n}")
+
+
+@pytest.mark.parametrize("seed,r", CASES[:2])
+def test_dumped_values_fold_to_the_production_digests(seed, r):
+    """The dump and the kernel that runs in production are the same stage
+    code: folding what one prints gives what every wave of the other
+    compares."""
+    for lds_bytes in (4096, FULL_LDS):
+        prod = cc.wave_digests(seed, r + 1, blocks=1, lds_bytes=lds_bytes)[:, r, :]
+        assert prod.shape == (16, 4)
+        for stage in range(3):
+            folded = cc.fold_values(stage, cc.wave_values(seed, stage, r, lds_bytes))
+            assert prod[:, stage].tolist() == [int(folded)] * 16, (stage, lds_bytes)
+        waves = range(16) if lds_bytes == 4096 else (0, 15)
+        for wave in waves:
+            folded = cc.fold_values(3, cc.wave_values(seed, 3, r, lds_bytes, wave))
+            assert int(prod[wave, 3]) == int(folded), (wave, lds_bytes)
 
 
 # 1. every wave against the reference --------------------------------------------
@@ -158,6 +245,20 @@ def test_argument_checks():
             run(d=torch.zeros(numel, dtype=torch.int32, device="cuda"))
     with pytest.raises(RuntimeError, match="inject"):
         e.cucheck_run(exp2, 0, 2, 1, 4096, 4, None, (16, 0, 0, 1))  # wave past the grid
+    # cucheck_values(seed, stage, round, lds_bytes, wave)
+    for args in ((0, 4, 0), (0, -1, 0), (0, 0, 65536), (0, 0, -1), (1 << 32, 0, 0),
+                 (0, 3, 0, 4096, 16), (0, 3, 0, 4096, -1)):
+        with pytest.raises(RuntimeError, match="cucheck"):
+            e.cucheck_values(*args)
+    for what, args in (("stage", (0, 4, 0)), ("round", (0, 0, 65536)), ("seed", (1 << 32, 0, 0)),
+                       ("wave", (0, 3, 0, 4096, 16))):
+        with pytest.raises(RuntimeError, match=what):
+            e.cucheck_values(*args)
+    for lds_bytes in (0, 2048, 6144, FULL_LDS + 4096):
+        with pytest.raises(RuntimeError, match="cucheck: lds_bytes"):
+            e.cucheck_values(0, 3, 0, lds_bytes, 0)
+    with pytest.raises(ValueError):
+        cc.wave_values(0, 4, 0)
     with pytest.raises(ValueError):
         cc.cucheck(rounds=0)
     with pytest.raises(ValueError):
