@@ -12,7 +12,9 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           atomic-unit integrity (atomcheck) and
                           host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
-                          csrc/pattern_common.h, cucheck, mxcheck,
+                          csrc/pattern_common.h (patterns, mismatch
+                          accounting, host-side argument checks and
+                          pattern-family dispatch), cucheck, mxcheck,
                           fpcheck and atomcheck csrc/cucheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 

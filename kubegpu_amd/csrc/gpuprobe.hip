@@ -308,6 +308,27 @@ static void check_timed_args(int64_t nbytes, int64_t iters) {
 // kernel that wrote nothing would pass the self-check.
 #define POISON 0xA5
 
+// The timed loop of the three probes: three untimed launches, then
+// `iters` launches between two events; returns their milliseconds.  The
+// events are destroyed before a launch error is raised.
+template <typename Launch>
+static float timed_ms(hipStream_t stream, int64_t iters, Launch&& launch) {
+  for (int w = 0; w < 3; ++w) launch();
+  hipEvent_t t0, t1;
+  (void)hipEventCreate(&t0);
+  (void)hipEventCreate(&t1);
+  (void)hipEventRecord(t0, stream);
+  for (int64_t i = 0; i < iters; ++i) launch();
+  (void)hipEventRecord(t1, stream);
+  (void)hipEventSynchronize(t1);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, t0, t1);
+  (void)hipEventDestroy(t0);
+  (void)hipEventDestroy(t1);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return ms;
+}
+
 // Timed device-to-device streaming copy; returns achieved GB/s
 // (bytes read + bytes written over wall time, hipEvent-timed).
 // blocks=0 picks the default; nontemporal selects the NT variant.
@@ -326,23 +347,10 @@ double copy_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg,
   src.fill_(1);
   dst.fill_(POISON);
   auto stream = at::hip::getCurrentHIPStream();
-  auto launch = [&]() {
+  float ms = timed_ms(stream, iters, [&]() {
     launch_copy(src.data_ptr(), dst.data_ptr(), n4, variant, nontemporal, blocks,
                 threads, stream);
-  };
-  for (int w = 0; w < 3; ++w) launch();
-  hipEvent_t t0, t1;
-  (void)hipEventCreate(&t0);
-  (void)hipEventCreate(&t1);
-  (void)hipEventRecord(t0, stream);
-  for (int64_t i = 0; i < iters; ++i) launch();
-  (void)hipEventRecord(t1, stream);
-  (void)hipEventSynchronize(t1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  C10_HIP_KERNEL_LAUNCH_CHECK();
+  });
   TORCH_CHECK(at::equal(dst, src), "copy_bw_gbps: variant ", variant,
               " produced wrong output");
   double sec = ms / 1e3;
@@ -357,20 +365,9 @@ double write_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
   at::Tensor dst = at::empty({nbytes}, opts);
   dst.fill_(POISON);
   auto stream = at::hip::getCurrentHIPStream();
-  auto launch = [&]() { launch_fill(dst.data_ptr(), n4, 0x01010101u, blocks, stream); };
-  for (int w = 0; w < 3; ++w) launch();
-  hipEvent_t t0, t1;
-  (void)hipEventCreate(&t0);
-  (void)hipEventCreate(&t1);
-  (void)hipEventRecord(t0, stream);
-  for (int64_t i = 0; i < iters; ++i) launch();
-  (void)hipEventRecord(t1, stream);
-  (void)hipEventSynchronize(t1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  C10_HIP_KERNEL_LAUNCH_CHECK();
+  float ms = timed_ms(stream, iters, [&]() {
+    launch_fill(dst.data_ptr(), n4, 0x01010101u, blocks, stream);
+  });
   // every byte is 0x01 iff min == max == 1 (a sum alone is met by
   // other contents too)
   TORCH_CHECK(dst.min().item<uint8_t>() == 1 && dst.max().item<uint8_t>() == 1,
@@ -389,22 +386,9 @@ double read_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
   src.fill_(1);
   at::Tensor out = at::zeros({1}, at::TensorOptions().dtype(at::kLong).device(at::kCUDA));
   auto stream = at::hip::getCurrentHIPStream();
-  auto launch = [&]() {
+  float ms = timed_ms(stream, iters, [&]() {
     launch_read_sum(src.data_ptr(), n4, out.data_ptr(), blocks, stream);
-  };
-  for (int w = 0; w < 3; ++w) launch();
-  hipEvent_t t0, t1;
-  (void)hipEventCreate(&t0);
-  (void)hipEventCreate(&t1);
-  (void)hipEventRecord(t0, stream);
-  for (int64_t i = 0; i < iters; ++i) launch();
-  (void)hipEventRecord(t1, stream);
-  (void)hipEventSynchronize(t1);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, t0, t1);
-  (void)hipEventDestroy(t0);
-  (void)hipEventDestroy(t1);
-  C10_HIP_KERNEL_LAUNCH_CHECK();
+  });
   // every launch adds the whole buffer's words to out: a kernel that
   // read less would report too high a bandwidth
   uint64_t want = (uint64_t)(3 + iters) * ((uint64_t)nbytes / 4) * 0x01010101ULL;

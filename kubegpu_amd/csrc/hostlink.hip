@@ -43,7 +43,6 @@
 // GB/s, against 38.4 for 8 + 8, 76.9 for 64 + 64 and 82.2 for 1024 +
 // 1024 in that file's duplex sweep.
 #define DEFAULT_WRITE_BLOCKS 8
-#define MAX_BLOCKS (1 << 20)
 
 // Grid-stride bodies over one role's own buffer with its own block
 // count: `block` of `nblocks` (the launch's for the single-role
@@ -154,51 +153,7 @@ static uint4v* check_host(const at::Tensor& host, const char* what) {
   return (uint4v*)dev;
 }
 
-static void check_pattern(int64_t pattern) {
-  TORCH_CHECK(pattern >= 0 && pattern < N_PATTERNS, "hostlink: pattern id ", pattern,
-              " out of range 0..", N_PATTERNS - 1);
-}
-
-static unsigned int check_seed(int64_t seed) {
-  TORCH_CHECK(seed >= 0 && seed <= 0xFFFFFFFFLL, "hostlink: seed must be a u32");
-  return (unsigned int)seed;
-}
-
-// first_vector -> the kernels' u64 base.  The binding is int64, and
-// first_vector + n4 must not wrap: at most 2^63.
-static u64 check_first(int64_t first_vector, size_t n4, const char* what) {
-  TORCH_CHECK(first_vector >= 0, "hostlink: ", what, " must not be negative, got ",
-              first_vector);
-  TORCH_CHECK((u64)first_vector + (u64)n4 <= (1ULL << 63), "hostlink: ", what, " ",
-              first_vector, " + ", n4, " vectors exceeds 2^63");
-  return (u64)first_vector;
-}
-
-static void check_blocks(int64_t blocks_arg) {
-  TORCH_CHECK(blocks_arg >= 0 && blocks_arg <= MAX_BLOCKS,
-              "hostlink: blocks must be in 0..", MAX_BLOCKS, ", got ", blocks_arg);
-}
-
-// 0 = the default grid, cut down to the buffer; never less than 1.
-static unsigned int pick_blocks(int64_t blocks_arg, size_t n4, int dflt) {
-  if (blocks_arg > 0) return (unsigned int)blocks_arg;
-  return (unsigned int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, (size_t)dflt);
-}
-
-static void check_max_records(int64_t max_records) {
-  TORCH_CHECK(max_records >= 0 && max_records <= MAX_RECORDS_LIMIT,
-              "hostlink: max_records must be in 0..", MAX_RECORDS_LIMIT);
-}
-
-static at::Tensor make_result(int device, int64_t max_records) {
-  at::Tensor res = at::zeros(
-      {RES_HEADER + 2 * max_records},
-      at::TensorOptions().dtype(at::kLong).device(at::kCUDA, (c10::DeviceIndex)device));
-  res.select(0, RES_FIRST).fill_(-1);  // u64 max: identity for atomicMin
-  return res;
-}
-
-static unsigned int inv_of(int64_t pattern) { return (pattern & 1) ? 0xFFFFFFFFu : 0u; }
+static const char* const WHO = "hostlink";
 
 // Pinned, mapped, fine-grained host memory as a CPU uint8 tensor.  The
 // coherent flag is explicit: the runtime's default depends on an
@@ -226,32 +181,22 @@ at::Tensor hostlink_alloc(int64_t nbytes, int64_t device_arg) {
 // could be handed to someone else.
 void hostlink_fill(at::Tensor host, int64_t pattern, int64_t seed_arg,
                    int64_t device_arg, int64_t blocks_arg, int64_t first_vector) {
-  check_pattern(pattern);
-  unsigned int seed = check_seed(seed_arg);
-  check_blocks(blocks_arg);
+  check_pattern(WHO, pattern);
+  unsigned int seed = check_seed(WHO, seed_arg);
+  check_blocks(WHO, blocks_arg);
   int device = check_device(device_arg);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(
       at::Device(at::kCUDA, (c10::DeviceIndex)device));
   uint4v* p = check_host(host, "host");
   size_t n4 = host.nbytes() / 16;
-  u64 first = check_first(first_vector, n4, "first_vector");
+  u64 first = check_first(WHO, first_vector, n4, "first_vector");
   unsigned int blocks = pick_blocks(blocks_arg, n4, DEFAULT_WRITE_BLOCKS);
   unsigned int inv = inv_of(pattern);
   hipStream_t stream = at::hip::getCurrentHIPStream((c10::DeviceIndex)device);
-  switch (pattern >> 1) {
-    case 0:
-      hipLaunchKernelGGL(hostlink_fill_kernel<0>, dim3(blocks), dim3(BLOCK), 0, stream,
-                         p, n4, first, seed, inv);
-      break;
-    case 1:
-      hipLaunchKernelGGL(hostlink_fill_kernel<1>, dim3(blocks), dim3(BLOCK), 0, stream,
-                         p, n4, first, seed, inv);
-      break;
-    default:
-      hipLaunchKernelGGL(hostlink_fill_kernel<2>, dim3(blocks), dim3(BLOCK), 0, stream,
-                         p, n4, first, seed, inv);
-      break;
-  }
+  with_family(pattern, [&](auto f) {
+    hipLaunchKernelGGL(hostlink_fill_kernel<decltype(f)::value>, dim3(blocks),
+                       dim3(BLOCK), 0, stream, p, n4, first, seed, inv);
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   C10_HIP_CHECK(hipStreamSynchronize(stream));
 }
@@ -259,62 +204,41 @@ void hostlink_fill(at::Tensor host, int64_t pattern, int64_t seed_arg,
 VerifyOut hostlink_verify(at::Tensor host, int64_t pattern, int64_t seed_arg,
                           int64_t device_arg, int64_t max_records,
                           int64_t blocks_arg, int64_t first_vector) {
-  check_pattern(pattern);
-  unsigned int seed = check_seed(seed_arg);
-  check_blocks(blocks_arg);
-  check_max_records(max_records);
+  check_pattern(WHO, pattern);
+  unsigned int seed = check_seed(WHO, seed_arg);
+  check_blocks(WHO, blocks_arg);
+  check_max_records(WHO, max_records);
   int device = check_device(device_arg);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(
       at::Device(at::kCUDA, (c10::DeviceIndex)device));
   const uint4v* p = check_host(host, "host");
   size_t n4 = host.nbytes() / 16;
-  u64 first = check_first(first_vector, n4, "first_vector");
+  u64 first = check_first(WHO, first_vector, n4, "first_vector");
   unsigned int blocks = pick_blocks(blocks_arg, n4, DEFAULT_READ_BLOCKS);
   unsigned int inv = inv_of(pattern);
   at::Tensor res = make_result(device, max_records);
   hipStream_t stream = at::hip::getCurrentHIPStream((c10::DeviceIndex)device);
   u64* r = (u64*)res.data_ptr();
   int mr = (int)max_records;
-  switch (pattern >> 1) {
-    case 0:
-      hipLaunchKernelGGL(hostlink_verify_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv, r, mr);
-      break;
-    case 1:
-      hipLaunchKernelGGL(hostlink_verify_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv, r, mr);
-      break;
-    default:
-      hipLaunchKernelGGL(hostlink_verify_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv, r, mr);
-      break;
-  }
+  with_family(pattern, [&](auto f) {
+    hipLaunchKernelGGL(hostlink_verify_kernel<decltype(f)::value>, dim3(blocks),
+                       dim3(BLOCK), 0, stream, p, n4, first, seed, inv, r, mr);
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return read_result(res, max_records, stream);
 }
-
-#define DUPLEX_LAUNCH(R, W)                                                     \
-  hipLaunchKernelGGL((hostlink_duplex_kernel<R, W>), dim3(rblocks + wblocks),   \
-                     dim3(BLOCK), 0, stream, rp, rn4, rfirst, rinv, wp, wn4, wfirst, \
-                     winv, seed, rblocks, r, mr)
-#define DUPLEX_WRITE(R)                 \
-  switch (write_pattern >> 1) {         \
-    case 0: DUPLEX_LAUNCH(R, 0); break; \
-    case 1: DUPLEX_LAUNCH(R, 1); break; \
-    default: DUPLEX_LAUNCH(R, 2); break; \
-  }
 
 VerifyOut hostlink_duplex(at::Tensor read_host, int64_t read_pattern,
                           at::Tensor write_host, int64_t write_pattern,
                           int64_t seed_arg, int64_t device_arg, int64_t max_records,
                           int64_t read_blocks_arg, int64_t write_blocks_arg,
                           int64_t read_first_vector, int64_t write_first_vector) {
-  check_pattern(read_pattern);
-  check_pattern(write_pattern);
-  unsigned int seed = check_seed(seed_arg);
-  check_blocks(read_blocks_arg);
-  check_blocks(write_blocks_arg);
-  check_max_records(max_records);
+  check_pattern(WHO, read_pattern);
+  check_pattern(WHO, write_pattern);
+  unsigned int seed = check_seed(WHO, seed_arg);
+  check_blocks(WHO, read_blocks_arg);
+  check_blocks(WHO, write_blocks_arg);
+  check_max_records(WHO, max_records);
   int device = check_device(device_arg);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(
       at::Device(at::kCUDA, (c10::DeviceIndex)device));
@@ -324,8 +248,8 @@ VerifyOut hostlink_duplex(at::Tensor read_host, int64_t read_pattern,
   TORCH_CHECK(ra + read_host.nbytes() <= wa || wa + write_host.nbytes() <= ra,
               "hostlink: read_host and write_host overlap");
   size_t rn4 = read_host.nbytes() / 16, wn4 = write_host.nbytes() / 16;
-  u64 rfirst = check_first(read_first_vector, rn4, "read_first_vector");
-  u64 wfirst = check_first(write_first_vector, wn4, "write_first_vector");
+  u64 rfirst = check_first(WHO, read_first_vector, rn4, "read_first_vector");
+  u64 wfirst = check_first(WHO, write_first_vector, wn4, "write_first_vector");
   unsigned int rblocks = pick_blocks(read_blocks_arg, rn4, DEFAULT_READ_BLOCKS);
   unsigned int wblocks = pick_blocks(write_blocks_arg, wn4, DEFAULT_WRITE_BLOCKS);
   unsigned int rinv = inv_of(read_pattern), winv = inv_of(write_pattern);
@@ -333,17 +257,17 @@ VerifyOut hostlink_duplex(at::Tensor read_host, int64_t read_pattern,
   hipStream_t stream = at::hip::getCurrentHIPStream((c10::DeviceIndex)device);
   u64* r = (u64*)res.data_ptr();
   int mr = (int)max_records;
-  switch (read_pattern >> 1) {
-    case 0: DUPLEX_WRITE(0); break;
-    case 1: DUPLEX_WRITE(1); break;
-    default: DUPLEX_WRITE(2); break;
-  }
+  with_family(read_pattern, [&](auto rf) {
+    with_family(write_pattern, [&](auto wf) {
+      hipLaunchKernelGGL(
+          (hostlink_duplex_kernel<decltype(rf)::value, decltype(wf)::value>),
+          dim3(rblocks + wblocks), dim3(BLOCK), 0, stream, rp, rn4, rfirst, rinv, wp, wn4,
+          wfirst, winv, seed, rblocks, r, mr);
+    });
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return read_result(res, max_records, stream);
 }
-
-#undef DUPLEX_WRITE
-#undef DUPLEX_LAUNCH
 
 // Called from gpuprobe.hip's PYBIND11_MODULE.  The GIL is released as
 // for the other probes: a pass over the link plus the stream synchronise

@@ -93,7 +93,7 @@ __global__ void verify_then_fill_kernel(uint4v* __restrict__ buf, size_t n4, u64
 
 // ---------------------------------------------------------------- host
 
-static size_t check_buf(const at::Tensor& buf, int64_t pattern) {
+static size_t check_buf(const at::Tensor& buf) {
   TORCH_CHECK(buf.is_cuda(), "memcheck: tensor must be on GPU");
   TORCH_CHECK(buf.is_contiguous(), "memcheck: tensor must be contiguous");
   TORCH_CHECK(buf.nbytes() > 0 && buf.nbytes() % 16 == 0,
@@ -101,141 +101,84 @@ static size_t check_buf(const at::Tensor& buf, int64_t pattern) {
               buf.nbytes());
   TORCH_CHECK((uintptr_t)buf.data_ptr() % 16 == 0,
               "memcheck: tensor storage must be 16-byte aligned");
-  TORCH_CHECK(pattern >= 0 && pattern < N_PATTERNS, "memcheck: pattern id ",
-              pattern, " out of range 0..", N_PATTERNS - 1);
   return buf.nbytes() / 16;
 }
 
-static int pick_blocks(int64_t blocks_arg, size_t n4, int dflt) {
-  TORCH_CHECK(blocks_arg >= 0 && blocks_arg <= (1 << 20),
-              "memcheck: blocks out of range");
-  if (blocks_arg > 0) return (int)blocks_arg;
-  return (int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, (size_t)dflt);
-}
-
-static unsigned int check_seed(int64_t seed) {
-  TORCH_CHECK(seed >= 0 && seed <= 0xFFFFFFFFLL, "memcheck: seed must be a u32");
-  return (unsigned int)seed;
-}
-
-// first_vector -> the kernels' u64 base.  The binding is int64, and
-// first_vector + n4 must not wrap: at most 2^63.
-static u64 check_first(int64_t first_vector, size_t n4) {
-  TORCH_CHECK(first_vector >= 0, "memcheck: first_vector must not be negative, got ",
-              first_vector);
-  TORCH_CHECK((u64)first_vector + (u64)n4 <= (1ULL << 63), "memcheck: first_vector ",
-              first_vector, " + ", n4, " vectors exceeds 2^63");
-  return (u64)first_vector;
-}
-
-static at::Tensor make_result(const at::Tensor& buf, int64_t max_records) {
-  TORCH_CHECK(max_records >= 0 && max_records <= MAX_RECORDS_LIMIT,
-              "memcheck: max_records must be in 0..", MAX_RECORDS_LIMIT);
-  at::Tensor res = at::zeros({RES_HEADER + 2 * max_records},
-                             buf.options().dtype(at::kLong));
-  res.select(0, RES_FIRST).fill_(-1);  // u64 max: identity for atomicMin
-  return res;
-}
+static const char* const WHO = "memcheck";
 
 void fill_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
                   int64_t blocks_arg, int64_t first_vector) {
-  size_t n4 = check_buf(buf, pattern);
-  unsigned int seed = check_seed(seed_arg);
-  u64 first = check_first(first_vector, n4);
-  int blocks = pick_blocks(blocks_arg, n4, DEFAULT_WRITE_BLOCKS);
+  size_t n4 = check_buf(buf);
+  check_pattern(WHO, pattern);
+  unsigned int seed = check_seed(WHO, seed_arg);
+  u64 first = check_first(WHO, first_vector, n4, "first_vector");
+  check_blocks(WHO, blocks_arg);
+  unsigned int blocks = pick_blocks(blocks_arg, n4, DEFAULT_WRITE_BLOCKS);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
   auto stream = at::hip::getCurrentHIPStream();
-  unsigned int inv = (pattern & 1) ? 0xFFFFFFFFu : 0u;
+  unsigned int inv = inv_of(pattern);
   uint4v* p = (uint4v*)buf.data_ptr();
-  switch (pattern >> 1) {
-    case 0:
-      hipLaunchKernelGGL(fill_pattern_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv);
-      break;
-    case 1:
-      hipLaunchKernelGGL(fill_pattern_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv);
-      break;
-    default:
-      hipLaunchKernelGGL(fill_pattern_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv);
-      break;
-  }
+  with_family(pattern, [&](auto f) {
+    hipLaunchKernelGGL(fill_pattern_kernel<decltype(f)::value>, dim3(blocks),
+                       dim3(BLOCK), 0, stream, p, n4, first, seed, inv);
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 VerifyOut verify_pattern(at::Tensor buf, int64_t pattern, int64_t seed_arg,
                          int64_t max_records, int64_t blocks_arg,
                          int64_t first_vector) {
-  size_t n4 = check_buf(buf, pattern);
-  unsigned int seed = check_seed(seed_arg);
-  u64 first = check_first(first_vector, n4);
-  int blocks = pick_blocks(blocks_arg, n4, VERIFY_BLOCKS);
+  size_t n4 = check_buf(buf);
+  check_pattern(WHO, pattern);
+  unsigned int seed = check_seed(WHO, seed_arg);
+  u64 first = check_first(WHO, first_vector, n4, "first_vector");
+  check_blocks(WHO, blocks_arg);
+  unsigned int blocks = pick_blocks(blocks_arg, n4, VERIFY_BLOCKS);
+  check_max_records(WHO, max_records);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
-  at::Tensor res = make_result(buf, max_records);
+  at::Tensor res = make_result(buf.get_device(), max_records);
   auto stream = at::hip::getCurrentHIPStream();
-  unsigned int inv =(pattern & 1) ? 0xFFFFFFFFu : 0u;
+  unsigned int inv = inv_of(pattern);
   const uint4v* p = (const uint4v*)buf.data_ptr();
   u64* r = (u64*)res.data_ptr();
   int mr = (int)max_records;
-  switch (pattern >> 1) {
-    case 0:
-      hipLaunchKernelGGL(verify_pattern_kernel<0>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv, r, mr);
-      break;
-    case 1:
-      hipLaunchKernelGGL(verify_pattern_kernel<1>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv, r, mr);
-      break;
-    default:
-      hipLaunchKernelGGL(verify_pattern_kernel<2>, dim3(blocks), dim3(BLOCK), 0,
-                         stream, p, n4, first, seed, inv, r, mr);
-      break;
-  }
+  with_family(pattern, [&](auto f) {
+    hipLaunchKernelGGL(verify_pattern_kernel<decltype(f)::value>, dim3(blocks),
+                       dim3(BLOCK), 0, stream, p, n4, first, seed, inv, r, mr);
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return read_result(res, max_records, stream);
 }
-
-#define VTF_LAUNCH(E, N)                                                       \
-  hipLaunchKernelGGL((verify_then_fill_kernel<E, N>), dim3(blocks), dim3(BLOCK), \
-                     0, stream, p, n4, first, seed, einv, ninv, r, mr)
-#define VTF_NEXT(E)                 \
-  switch (next_pattern >> 1) {      \
-    case 0: VTF_LAUNCH(E, 0); break; \
-    case 1: VTF_LAUNCH(E, 1); break; \
-    default: VTF_LAUNCH(E, 2); break; \
-  }
 
 VerifyOut verify_then_fill(at::Tensor buf, int64_t expect_pattern,
                            int64_t next_pattern, int64_t seed_arg,
                            int64_t max_records, int64_t blocks_arg,
                            int64_t first_vector) {
-  size_t n4 = check_buf(buf, expect_pattern);
-  TORCH_CHECK(next_pattern >= 0 && next_pattern < N_PATTERNS,
-              "memcheck: pattern id ", next_pattern, " out of range 0..",
-              N_PATTERNS - 1);
-  unsigned int seed = check_seed(seed_arg);
-  u64 first = check_first(first_vector, n4);
-  int blocks = pick_blocks(blocks_arg, n4, DEFAULT_COPY_BLOCKS);
+  size_t n4 = check_buf(buf);
+  check_pattern(WHO, expect_pattern);
+  check_pattern(WHO, next_pattern);
+  unsigned int seed = check_seed(WHO, seed_arg);
+  u64 first = check_first(WHO, first_vector, n4, "first_vector");
+  check_blocks(WHO, blocks_arg);
+  unsigned int blocks = pick_blocks(blocks_arg, n4, DEFAULT_COPY_BLOCKS);
+  check_max_records(WHO, max_records);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(buf));
-  at::Tensor res = make_result(buf, max_records);
+  at::Tensor res = make_result(buf.get_device(), max_records);
   auto stream = at::hip::getCurrentHIPStream();
-  unsigned int einv = (expect_pattern & 1) ? 0xFFFFFFFFu : 0u;
-  unsigned int ninv = (next_pattern & 1) ? 0xFFFFFFFFu : 0u;
+  unsigned int einv = inv_of(expect_pattern), ninv = inv_of(next_pattern);
   uint4v* p = (uint4v*)buf.data_ptr();
   u64* r = (u64*)res.data_ptr();
   int mr = (int)max_records;
-  switch (expect_pattern >> 1) {
-    case 0: VTF_NEXT(0); break;
-    case 1: VTF_NEXT(1); break;
-    default: VTF_NEXT(2); break;
-  }
+  with_family(expect_pattern, [&](auto e) {
+    with_family(next_pattern, [&](auto n) {
+      hipLaunchKernelGGL((verify_then_fill_kernel<decltype(e)::value, decltype(n)::value>),
+                         dim3(blocks), dim3(BLOCK), 0, stream, p, n4, first, seed, einv,
+                         ninv, r, mr);
+    });
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return read_result(res, max_records, stream);
 }
-
-#undef VTF_NEXT
-#undef VTF_LAUNCH
 
 // Called from gpuprobe.hip's PYBIND11_MODULE. The GIL is released for
 // the same reason as the timed probes: a pass over a large buffer plus

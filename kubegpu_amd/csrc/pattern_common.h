@@ -1,4 +1,5 @@
-// Pattern generation and mismatch accounting shared by the integrity
+// Pattern generation, mismatch accounting and the host side's argument
+// checks, result block and family dispatch shared by the integrity
 // kernels that stream a buffer: memcheck.hip (HBM) and hostlink.hip
 // (host memory over the PCIe link); both files compile into _gpuprobe.
 //
@@ -18,12 +19,15 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #define WAVE 64
 #define BLOCK 256
 #define N_PATTERNS 6
+#define MAX_BLOCKS (1 << 20)
 #define MAX_RECORDS_LIMIT 4096
 
 typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
@@ -156,9 +160,76 @@ __device__ __forceinline__ void reduce_tally(Tally t, u64* __restrict__ res) {
 }
 
 // ---------------------------------------------------------------- host
+//
+// Argument checks, the grid pick, the result block and the family
+// dispatch of both files' entry points.  `who` prefixes the error
+// messages ("memcheck" or "hostlink").
 
 typedef std::tuple<int64_t, int64_t, int64_t> Record;  // word, expected, got
 typedef std::tuple<int64_t, int64_t, int64_t, std::vector<Record>> VerifyOut;
+
+static inline unsigned int check_seed(const char* who, int64_t seed) {
+  TORCH_CHECK(seed >= 0 && seed <= 0xFFFFFFFFLL, who, ": seed must be a u32");
+  return (unsigned int)seed;
+}
+
+static inline void check_pattern(const char* who, int64_t pattern) {
+  TORCH_CHECK(pattern >= 0 && pattern < N_PATTERNS, who, ": pattern id ", pattern,
+              " out of range 0..", N_PATTERNS - 1);
+}
+
+// first_vector -> the kernels' u64 base.  The binding is int64, and
+// first_vector + n4 must not wrap: at most 2^63.
+static inline u64 check_first(const char* who, int64_t first_vector, size_t n4,
+                              const char* what) {
+  TORCH_CHECK(first_vector >= 0, who, ": ", what, " must not be negative, got ",
+              first_vector);
+  TORCH_CHECK((u64)first_vector + (u64)n4 <= (1ULL << 63), who, ": ", what, " ",
+              first_vector, " + ", n4, " vectors exceeds 2^63");
+  return (u64)first_vector;
+}
+
+static inline void check_blocks(const char* who, int64_t blocks_arg) {
+  TORCH_CHECK(blocks_arg >= 0 && blocks_arg <= MAX_BLOCKS, who,
+              ": blocks must be in 0..", MAX_BLOCKS, ", got ", blocks_arg);
+}
+
+// A checked blocks argument; 0 = the default grid, cut down to the
+// buffer; never less than 1.
+static inline unsigned int pick_blocks(int64_t blocks_arg, size_t n4, int dflt) {
+  if (blocks_arg > 0) return (unsigned int)blocks_arg;
+  return (unsigned int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, (size_t)dflt);
+}
+
+static inline void check_max_records(const char* who, int64_t max_records) {
+  TORCH_CHECK(max_records >= 0 && max_records <= MAX_RECORDS_LIMIT, who,
+              ": max_records must be in 0..", MAX_RECORDS_LIMIT);
+}
+
+// Zeroed result block for a checked max_records on GPU `device`.
+static inline at::Tensor make_result(int device, int64_t max_records) {
+  at::Tensor res = at::zeros(
+      {RES_HEADER + 2 * max_records},
+      at::TensorOptions().dtype(at::kLong).device(at::kCUDA, (c10::DeviceIndex)device));
+  res.select(0, RES_FIRST).fill_(-1);  // u64 max: identity for atomicMin
+  return res;
+}
+
+static inline unsigned int inv_of(int64_t pattern) {
+  return (pattern & 1) ? 0xFFFFFFFFu : 0u;
+}
+
+// Checked pattern id -> compile-time family: calls f with an
+// std::integral_constant, so that f can launch kernel<decltype(c)::value>.
+// The one place a pattern id picks a template argument.
+template <typename F>
+static inline void with_family(int64_t pattern, F&& f) {
+  switch (pattern >> 1) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    default: f(std::integral_constant<int, 2>{}); break;
+  }
+}
 
 // Wait for the stream, then unpack a result block (int64 tensor on the
 // GPU, RES_HEADER + 2 * max_records slots) into the Python tuple.

@@ -251,6 +251,26 @@ def test_duplex(read_blocks, write_blocks):
     assert rd.guards_intact() and wr.guards_intact()
 
 
+def test_duplex_every_pattern_pair():
+    """All 36 (read, write) pattern pairs through the nested family
+    dispatch: a wrong family or a swapped pair shows as mismatches on the
+    read side or as wrong words on the write side.  One workgroup per
+    role, both buffers ragged past one 256-thread stride, sizes differ."""
+    read_n, write_n = 4096 + 48, 4096 + 16
+    rd, wr = Guarded(read_n), Guarded(write_n)
+    for read_pattern in mc.PATTERNS:
+        for write_pattern in mc.PATTERNS:
+            pair = (read_pattern, write_pattern)
+            rd.write(read_pattern, 9)
+            wr.whole.fill_(SENTINEL)
+            r = hl.duplex(rd.buf, read_pattern, wr.buf, write_pattern, 9,
+                          read_blocks=1, write_blocks=1)
+            assert (r.mismatched_words, r.first_bad_offset, r.bad_bits_mask, r.records) == \
+                (0, None, 0, []), pair
+            assert np.array_equal(wr.words, ref(write_n // 16, write_pattern, 9)), pair
+            assert rd.guards_intact() and wr.guards_intact(), pair
+
+
 def test_duplex_rejects_overlap():
     g = Guarded(4096)
     cases = [
