@@ -27,6 +27,9 @@ Modes:
   amddevs --atomcheck     atomic-unit (LDS, L2 and memory-side atomics)
                           integrity probe over the idle GPUs, same shape and
                           exit codes ([--rounds N])
+  amddevs --lanecheck     cross-lane (DPP, LDS crossbar, readlane, permlane
+                          swaps) integrity probe over the idle GPUs, same
+                          shape and exit codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -40,7 +43,7 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import EXIT_CANNOT_RUN, HEALTH_PROBES
+from ..probe._active import ALL_PROBES, EXIT_CANNOT_RUN
 
 # probe -> (what the --fake backend lacks, size argument, name of its
 # default in the probe's module, result keys that count wrong data)
@@ -53,6 +56,7 @@ _PROBE_RUNS = {
                  ("mismatched_words", "cpu_sample_mismatches")),
     "atomcheck": ("atomic units", "rounds", "DEFAULT_ROUNDS",
                   ("mismatches", "shared_mismatches")),
+    "lanecheck": ("cross-lane paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
 }
 
 
@@ -110,7 +114,8 @@ def main(argv=None) -> int:
                    help="run the compute-unit integrity probe on every GPU "
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
-                   help="with --cucheck, --mxcheck, --fpcheck or --atomcheck: rounds per GPU "
+                   help="with --cucheck, --mxcheck, --fpcheck, --atomcheck or --lanecheck: rounds "
+                        "per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
@@ -127,6 +132,10 @@ def main(argv=None) -> int:
                    help="run the atomic-unit integrity probe (LDS, L2 and "
                         "memory-side atomics) on every GPU this command can "
                         "see no allocation on")
+    p.add_argument("--lanecheck", action="store_true",
+                   help="run the cross-lane integrity probe (DPP, LDS "
+                        "crossbar, readlane, permlane swaps) on every GPU this "
+                        "command can see no allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -157,7 +166,7 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    for probe in HEALTH_PROBES:
+    for probe in ALL_PROBES:
         if getattr(args, probe):
             return _run_probe(probe, args, backend)
     if args.health:
@@ -177,6 +186,7 @@ def main(argv=None) -> int:
                 "mxcheck": mgr.mxcheck_status(uuid),
                 "fpcheck": mgr.fpcheck_status(uuid),
                 "atomcheck": mgr.atomcheck_status(uuid),
+                "lanecheck": mgr.lanecheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

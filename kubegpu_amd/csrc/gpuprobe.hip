@@ -408,6 +408,8 @@ void bind_mxcheck(py::module_& m);
 void bind_fpcheck(py::module_& m);
 // Atomic-unit integrity kernel (atomcheck.hip, same extension).
 void bind_atomcheck(py::module_& m);
+// Cross-lane integrity kernel (lanecheck.hip, same extension).
+void bind_lanecheck(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
@@ -417,6 +419,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_mxcheck(m);
   bind_fpcheck(m);
   bind_atomcheck(m);
+  bind_lanecheck(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

@@ -43,7 +43,7 @@ from ..discovery import (
     default_backend,
 )
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import HEALTH_PROBES
+from ..probe._active import ALL_PROBES
 
 # Extracts the concrete GPU id out of a bound cards resource name
 # (cf. the reference's UUID regex at nvidia_gpu_manager.go:225).
@@ -90,7 +90,7 @@ class AMDGPUManager(Device):
         # the grace window expires: uuid -> (last GpuInfo, swept-at).
         self.vanished: Dict[str, tuple] = {}
         # Verdicts of the active probes, one dict per name in
-        # HEALTH_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
+        # ALL_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
         # because GpuInfo objects are replaced on every re-discovery and
         # the verdict must outlive them.
         # Active HBM integrity (memcheck) verdicts.
@@ -105,6 +105,8 @@ class AMDGPUManager(Device):
         self.hostlink: Dict[str, dict] = {}
         # Active atomic-unit integrity (atomcheck) verdicts, kept the same way.
         self.atomcheck: Dict[str, dict] = {}
+        # Active cross-lane integrity (lanecheck) verdicts, kept the same way.
+        self.lanecheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -196,7 +198,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
-                    for probe in HEALTH_PROBES:
+                    for probe in ALL_PROBES:
                         getattr(self, probe).pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
@@ -210,7 +212,7 @@ class AMDGPUManager(Device):
 
         Present GPUs are healthy unless they report uncorrectable ECC
         errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
-        mxcheck, fpcheck, hostlink or atomcheck verdict;
+        mxcheck, fpcheck, hostlink, atomcheck or lanecheck verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -225,7 +227,7 @@ class AMDGPUManager(Device):
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
         """ECC health AND no failed verdict of any active probe (lock
         held)."""
-        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in HEALTH_PROBES)
+        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in ALL_PROBES)
         return gpu.healthy and all(v is None or v["ok"] for v in verdicts)
 
     def _record(self, probe: str, uuid: str, result: dict, count_keys, describe) -> bool:
@@ -264,7 +266,7 @@ class AMDGPUManager(Device):
             return dict(v) if v is not None else None
 
     def _record_digests(self, probe: str, uuid: str, result: dict) -> bool:
-        """``_record`` for cucheck, mxcheck and fpcheck, whose results
+        """``_record`` for cucheck, mxcheck, fpcheck and lanecheck, whose results
         (``DigestResult.to_dict()``) count ``mismatches``."""
         return self._record(probe, uuid, result, ("mismatches",), lambda v: (
             probe + " FAILED on GPU %s: %d wrong digest(s), first bad round "
@@ -361,6 +363,15 @@ class AMDGPUManager(Device):
 
     def atomcheck_status(self, uuid: str) -> Optional[dict]:
         return self._status("atomcheck", uuid)
+
+    def record_lanecheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("lanecheck", uuid, result)
+
+    def clear_lanecheck(self, uuid: str) -> bool:
+        return self._clear("lanecheck", uuid)
+
+    def lanecheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("lanecheck", uuid)
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:

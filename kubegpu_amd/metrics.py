@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
-from .probe._active import HEALTH_PROBES
+from .probe._active import ALL_PROBES
 
 try:
     from prometheus_client import (
@@ -100,6 +100,16 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "atomcheck runs that could not complete (not an atomic-unit fault)"),
     ),
+    "lanecheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last cross-lane lanecheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last lanecheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed cross-lane lanecheck"),
+        ("err", "counter", "errors_total",
+         "lanecheck runs that could not complete (not a cross-lane fault)"),
+    ),
 }
 
 
@@ -113,7 +123,7 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         # gpu_<probe>: uuid -> what the last run's setter was given;
         # gpu_<probe>_errors: uuid -> runs that could not complete
-        for probe in HEALTH_PROBES:
+        for probe in ALL_PROBES:
             setattr(self, f"gpu_{probe}", {})
             setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
@@ -156,7 +166,7 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            for probe in HEALTH_PROBES:
+            for probe in ALL_PROBES:
                 for attr, kind, name, help_text in _PROBE_METRICS[probe]:
                     setattr(self, f"_{probe}_{attr}",
                             (Gauge if kind == "gauge" else Counter)(
@@ -277,6 +287,13 @@ class Metrics:
 
     def inc_atomcheck_error(self, uuid: str) -> None:
         self._inc_probe_error("atomcheck", uuid)
+
+    def set_gpu_lanecheck(self, uuid: str, mismatches: int, cus_covered: int,
+                          timestamp: float) -> None:
+        self._set_gpu_digests("lanecheck", uuid, mismatches, cus_covered, timestamp)
+
+    def inc_lanecheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("lanecheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

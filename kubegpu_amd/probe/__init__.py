@@ -95,6 +95,18 @@ _ATOMCHECK_EXPORTS = (
 )
 
 
+# Cross-lane integrity probe (probe/lanecheck.py), the same way; the
+# lanecheck() function is `kubegpu_amd.probe.lanecheck.lanecheck`.  Its
+# reference_digests / wave_digests / wave_values stay in the submodule
+# too.
+_LANECHECK_EXPORTS = (
+    "LanecheckResult",
+    "dpp_source",
+    "lanecheck_round",
+    "run_lanecheck_subprocess",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
@@ -102,6 +114,7 @@ _LAZY_EXPORTS = {
     "fpcheck": _FPCHECK_EXPORTS,
     "hostlink": _HOSTLINK_EXPORTS,
     "atomcheck": _ATOMCHECK_EXPORTS,
+    "lanecheck": _LANECHECK_EXPORTS,
 }
 
 

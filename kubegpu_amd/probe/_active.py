@@ -1,5 +1,5 @@
 """What the active integrity probes (memcheck, cucheck, mxcheck,
-fpcheck, hostlink, atomcheck) share: the exit codes, the one child-process lock,
+fpcheck, hostlink, atomcheck, lanecheck) share: the exit codes, the one child-process lock,
 the child runner, the round over a node's idle GPUs and the CLI body.
 Each probe module binds these to its own name, so a probe adds only
 what is its own: kernels, reference, result type.
@@ -20,10 +20,12 @@ from typing import Callable, Dict, List, Optional, Tuple
 # In the order the manager, the metrics, the agent and the CLI go
 # through them.
 ACTIVE_PROBES: Tuple[str, ...] = ("memcheck", "cucheck", "mxcheck", "fpcheck", "hostlink")
-# Every probe whose verdict decides a GPU's health: what the manager,
-# the metrics, the agent loop and the CLI iterate.  ACTIVE_PROBES stays
-# the first five; later probes are appended here.
+# ACTIVE_PROBES stays the first five and HEALTH_PROBES the first six.
 HEALTH_PROBES: Tuple[str, ...] = ACTIVE_PROBES + ("atomcheck",)
+# Every probe whose verdict decides a GPU's health: what the manager,
+# the metrics, the agent loop and the CLI iterate; later probes are
+# appended here.
+ALL_PROBES: Tuple[str, ...] = HEALTH_PROBES + ("lanecheck",)
 
 EXIT_PASS, EXIT_MISMATCH, EXIT_CANNOT_RUN = 0, 1, 2
 

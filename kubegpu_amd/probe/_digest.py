@@ -1,5 +1,5 @@
-"""What the digest probes (cucheck, mxcheck, fpcheck, atomcheck) share on
-the host: the hash that generates their inputs, the result type, the
+"""What the digest probes (cucheck, mxcheck, fpcheck, atomcheck, lanecheck)
+share on the host: the hash that generates their inputs, the result type, the
 decoding of the kernel's result block and the dump run.  Their kernels
 share csrc/cucheck_common.h the same way.
 
@@ -180,6 +180,6 @@ def wave_digests(name: str, run, table, stages: Sequence[str], seed: int, rounds
 
 
 def metric_args(rec: dict) -> tuple:
-    """What ``set_gpu_cucheck`` / ``_mxcheck`` / ``_fpcheck`` take of a
-    result dict, before the timestamp."""
+    """What ``set_gpu_cucheck`` / ``_mxcheck`` / ``_fpcheck`` / ``_lanecheck``
+    take of a result dict, before the timestamp."""
     return int(rec["mismatches"]), int(rec.get("cus_covered", 0))
