@@ -535,34 +535,29 @@ AT_DEV void at_shared(u64* sh, u32 seed, u32 rp, u32 gwave, u32 lane) {
 #endif  // __HIP_DEVICE_COMPILE__
 
 __global__ void __launch_bounds__(CU_BLOCK)
-atomcheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
-                 u32* __restrict__ res, int max_records, u32* __restrict__ dump,
-                 u64* arena, u64* shared, u32 shared_every, u32 drop_wave, u32 drop_round,
-                 u32 inj_wave, u32 inj_round, u32 inj_stage, u32 inj_mask) {
+atomcheck_kernel(CuArgs a, u64* arena, u64* shared, u32 shared_every, u32 drop_wave,
+                 u32 drop_round) {
 #if __HIP_DEVICE_COMPILE__
   extern __shared__ u64 at_lds[];
-  const int lane = threadIdx.x % WAVE;
-  const u32 wib = threadIdx.x / WAVE;
-  const u32 gwave = blockIdx.x * CU_WAVES + wib;
-  const u32 hw = cu_locate_wave(res, lane);
+  const CuWave w = cu_wave(a);
+  const u32 lane = (u32)w.lane, wib = threadIdx.x / WAVE;
   u64* lslice = at_lds + wib * AT_SLICE;
   u32* xc = (u32*)(at_lds + CU_WAVES * AT_SLICE);
-  u64* gslice = arena + (size_t)gwave * AT_WAVE_CELLS;
+  u64* gslice = arena + (size_t)w.gwave * AT_WAVE_CELLS;
 
-  for (u32 r = 0; r < rounds; ++r) {
+  for (u32 r = 0; r < a.rounds; ++r) {
     const u32 rp = r % AT_PERIOD;
     AtFold f0, f1, f2, f3;
-    at_stage_lds(lslice, xc, cu_base(seed, AT_STAGE0 + 0, rp), wib, (u32)lane, f0);
-    at_stage_g32(gslice, cu_base(seed, AT_STAGE0 + 1, rp), (u32)lane, f1);
-    at_stage_g64(gslice + AT_SLICE, cu_base(seed, AT_STAGE0 + 2, rp), (u32)lane, f2);
-    at_stage_gfp(gslice + 2 * AT_SLICE, cu_base(seed, AT_STAGE0 + 3, rp), (u32)lane, f3);
+    at_stage_lds(lslice, xc, cu_base(a.seed, AT_STAGE0 + 0, rp), wib, lane, f0);
+    at_stage_g32(gslice, cu_base(a.seed, AT_STAGE0 + 1, rp), lane, f1);
+    at_stage_g64(gslice + AT_SLICE, cu_base(a.seed, AT_STAGE0 + 2, rp), lane, f2);
+    at_stage_gfp(gslice + 2 * AT_SLICE, cu_base(a.seed, AT_STAGE0 + 3, rp), lane, f3);
     if (shared_every != 0u && r % shared_every == 0u &&
-        !(gwave == drop_wave && r == drop_round))
-      at_shared(shared, seed, rp, gwave, (u32)lane);
+        !(w.gwave == drop_wave && r == drop_round))
+      at_shared(shared, a.seed, rp, w.gwave, lane);
     u32 dig[N_STAGES] = {wave_sum(f0.d), wave_sum(f1.d), wave_sum(f2.d), wave_sum(f3.d)};
 
-    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
-                   inj_wave, inj_round, inj_stage, inj_mask);
+    cu_check_round(dig, r, w, a);
   }
 #endif
 }
@@ -637,11 +632,9 @@ CucheckOut atomcheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
   }
   u64* cells = (u64*)arena.data_ptr();
 
-  return cu_launch_timed(atomcheck_kernel, l, MAX_LDS_BYTES, max_records, (u32)seed_arg,
-                         (u32)rounds, (const u32*)expected.data_ptr(),
-                         (u32*)l.res.data_ptr(), (int)max_records, l.dump, cells,
+  return cu_launch_timed(atomcheck_kernel, l, MAX_LDS_BYTES, cells,
                          cells + waves * AT_WAVE_CELLS, (u32)shared_every, drop_wave,
-                         drop_round, l.inj_wave, l.inj_round, l.inj_stage, l.inj_mask);
+                         drop_round);
 }
 
 // What wave 0 folds for one stage and round as an int64 tensor on the
@@ -652,13 +645,9 @@ at::Tensor atomcheck_values(int64_t seed_arg, int64_t stage, int64_t round) {
   auto opts = at::TensorOptions().dtype(at::kLong).device(at::kCUDA);
   at::Tensor out = at::zeros({(int64_t)(64 * AT_VALUE_SLOTS + 1)}, opts);
   at::Tensor arena = at::zeros({(int64_t)(CU_WAVES * AT_WAVE_CELLS)}, opts);
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(atomcheck_values_kernel, dim3(1), dim3(CU_BLOCK), (size_t)AT_LDS_USED,
-                     stream, (u32)seed_arg, (u32)stage, (u32)round, (u64*)arena.data_ptr(),
-                     (u64*)out.data_ptr());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  C10_HIP_CHECK(hipStreamSynchronize(stream));
-  return out;
+  return cu_launch_values(atomcheck_values_kernel, CU_BLOCK, AT_LDS_USED, out, (u32)seed_arg,
+                          (u32)stage, (u32)round, (u64*)arena.data_ptr(),
+                          (u64*)out.data_ptr());
 }
 
 // Called from gpuprobe.hip's PYBIND11_MODULE; GIL released like the

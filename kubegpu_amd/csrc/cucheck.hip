@@ -179,29 +179,25 @@ __device__ __forceinline__ void cu_stage_lds(u32 base, u32* slice, u32 lds_dword
 }
 
 __global__ void __launch_bounds__(CU_BLOCK)
-cucheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
-               u32* __restrict__ res, int max_records, u32* __restrict__ dump,
-               u32 lds_dwords, u32 inj_wave, u32 inj_round, u32 inj_stage,
-               u32 inj_mask) {
+cucheck_kernel(CuArgs a, u32 lds_dwords) {
 #if __HIP_DEVICE_COMPILE__
   extern __shared__ u32 lds[];
+  // not w.lane: with it wave_sum's shuffle addresses stay live across the
+  // round loop, 82 VGPRs instead of 80, one occupancy step
   const int lane = threadIdx.x % WAVE;
-  const u32 wib = threadIdx.x / WAVE;
-  const u32 gwave = blockIdx.x * CU_WAVES + wib;
-  const u32 hw = cu_locate_wave(res, lane);
+  const CuWave w = cu_wave(a);
   const u32 rc = lane & 31, half = lane >> 5;
-  u32* slice = lds + wib * lds_dwords;
+  u32* slice = lds + threadIdx.x / WAVE * lds_dwords;
 
-  for (u32 r = 0; r < rounds; ++r) {
+  for (u32 r = 0; r < a.rounds; ++r) {
     CuFold f0, f1, f2, f3;
-    cu_stage_i8(cu_base(seed, 0, r), rc, half, lane, f0);
-    cu_stage_bf16(cu_base(seed, 1, r), rc, half, lane, f1);
-    cu_stage_valu(cu_base(seed, 2, r), lane, f2);
-    cu_stage_lds(cu_base(seed, 3, r), slice, lds_dwords, lane, f3);
+    cu_stage_i8(cu_base(a.seed, 0, r), rc, half, lane, f0);
+    cu_stage_bf16(cu_base(a.seed, 1, r), rc, half, lane, f1);
+    cu_stage_valu(cu_base(a.seed, 2, r), lane, f2);
+    cu_stage_lds(cu_base(a.seed, 3, r), slice, lds_dwords, lane, f3);
     u32 dig[N_STAGES] = {f0.dig, f1.dig, f2.dig, f3.dig};
 
-    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
-                   inj_wave, inj_round, inj_stage, inj_mask);
+    cu_check_round(dig, r, w, a);
   }
   // keep the workgroup's LDS allocated until all its waves are done
   __syncthreads();
@@ -252,12 +248,7 @@ CucheckOut cucheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
   CuLaunch l = cu_prepare("cucheck", expected, seed_arg, rounds, blocks_arg,
                           max_records, dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
-
-  return cu_launch_timed(cucheck_kernel, l, lds_bytes, max_records, (u32)seed_arg,
-                         (u32)rounds, (const u32*)expected.data_ptr(),
-                         (u32*)l.res.data_ptr(), (int)max_records, l.dump,
-                         (u32)(lds_bytes / 4 / CU_WAVES), l.inj_wave, l.inj_round,
-                         l.inj_stage, l.inj_mask);
+  return cu_launch_timed(cucheck_kernel, l, lds_bytes, (u32)(lds_bytes / 4 / CU_WAVES));
 }
 
 // The values wave `wave` of one workgroup computed for one stage and
@@ -274,16 +265,9 @@ at::Tensor cucheck_values(int64_t seed_arg, int64_t stage, int64_t round,
   const int64_t cols = stage == 3 ? lds_dwords : stage == 2 ? WAVE : 32;
   at::Tensor out =
       at::zeros({rows, cols}, at::TensorOptions().dtype(at::kLong).device(at::kCUDA));
-  C10_HIP_CHECK(hipFuncSetAttribute((const void*)cucheck_values_kernel,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_bytes));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(cucheck_values_kernel, dim3(1), dim3(CU_BLOCK), (size_t)lds_bytes,
-                     stream, (u32)seed_arg, (u32)stage, (u32)round, (u32)lds_dwords,
-                     (u32)wave, (long long*)out.data_ptr());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  C10_HIP_CHECK(hipStreamSynchronize(stream));
-  return out;
+  return cu_launch_values(cucheck_values_kernel, CU_BLOCK, lds_bytes, out, (u32)seed_arg,
+                          (u32)stage, (u32)round, (u32)lds_dwords, (u32)wave,
+                          (long long*)out.data_ptr());
 }
 
 // Called from gpuprobe.hip's PYBIND11_MODULE; GIL released like the

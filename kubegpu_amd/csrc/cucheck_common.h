@@ -1,19 +1,19 @@
-// Hashing, digest folding, the per-round compare, mismatch accounting,
-// launch arguments and the timed launch shared by the integrity kernels
-// that run one 16-wave workgroup per compute unit; all three files
-// compile into _gpuprobe and add only their stages:
-//   cucheck.hip  i8 / bf16 matrix cores, VALU, LDS (the one kernel that
-//                uses its dynamic LDS, hence its lds_dwords argument), and
-//                a single-wave launcher that returns a stage's values
-//   mxcheck.hip  f16 / fp8 / MXFP4 / f64 matrix cores, and a single-wave
-//                launcher that returns one accumulator tile
-//   fpcheck.hip  IEEE rounding of the vector FP units, and a single-wave
-//                launcher that returns one round's raw result bits
+// Hashing, digest folding, the kernels' argument block, the per-round
+// compare, mismatch accounting, argument checks, the timed launch and the
+// single-wave value launch shared by the integrity kernels that run one
+// 16-wave workgroup per compute unit; all five files compile into
+// _gpuprobe and add only their stages, a fold / dump pair of sinks for
+// the stages' values and their own kernel arguments:
+//   cucheck.hip    i8 / bf16 matrix cores, VALU, LDS (lds_dwords)
+//   mxcheck.hip    f16 / fp8 / MXFP4 / f64 matrix cores
+//   fpcheck.hip    IEEE rounding of the vector FP units
+//   atomcheck.hip  LDS, L2 and memory-side atomics (arena, shared, drop)
+//   lanecheck.hip  the cross-lane data paths
 //
 // Every wave compares N_STAGES 32-bit digests per round with a table the
 // host computed in numpy.  Inputs are word(stage, r, idx) =
-// fmix32(base(seed, stage, r) + idx); probe/cucheck.py, probe/mxcheck.py
-// and probe/fpcheck.py hold the numpy definitions.
+// fmix32(base(seed, stage, r) + idx); the probe/<name>.py of each kernel
+// holds the numpy definition.
 
 #pragma once
 
@@ -72,6 +72,17 @@ __device__ __forceinline__ u32 wave_sum(u32 v) {
   return v;
 }
 
+// What every digest kernel takes first, by value (cu_prepare fills it);
+// its own arguments follow.  inj_*: the test hook of cu_check_round.
+struct CuArgs {
+  u32 seed, rounds;
+  const u32* expected;  // [rounds, N_STAGES]
+  u32* res;             // the result block above
+  int max_records;
+  u32* dump;  // [waves, rounds, N_STAGES] or null
+  u32 inj_wave, inj_round, inj_stage, inj_mask;
+};
+
 // Where the hardware says this wave runs, read once: xcc<<16 |
 // HW_ID[15:0].  Lane 0 counts the wave in the per-CU table.
 __device__ __forceinline__ u32 cu_locate_wave(u32* __restrict__ res, int lane) {
@@ -87,6 +98,17 @@ __device__ __forceinline__ u32 cu_locate_wave(u32* __restrict__ res, int lane) {
 #else
   return 0;
 #endif
+}
+
+// Every kernel opens with this: lane, wave of the grid, where it runs.
+struct CuWave {
+  int lane;
+  u32 gwave, hw;
+};
+
+__device__ __forceinline__ CuWave cu_wave(const CuArgs& a) {
+  const int lane = threadIdx.x % WAVE;
+  return {lane, blockIdx.x * CU_WAVES + threadIdx.x / WAVE, cu_locate_wave(a.res, lane)};
 }
 
 // Mismatch path only (never taken on a healthy GPU): count, lowest bad
@@ -116,26 +138,24 @@ static __device__ __noinline__ void log_mismatch(u32* __restrict__ res, int max_
 // hook works on a copy of the digests: on values the compiler keeps it
 // to four selects, through the caller's array it builds a branch tree
 // and allocates the kernel's registers differently.
-__device__ __forceinline__ void cu_check_round(
-    const u32 (&digests)[N_STAGES], u32 r, u32 rounds, int lane, u32 gwave, u32 hw,
-    const u32* __restrict__ expected, u32* __restrict__ res, int max_records,
-    u32* __restrict__ dump, u32 inj_wave, u32 inj_round, u32 inj_stage, u32 inj_mask) {
+__device__ __forceinline__ void cu_check_round(const u32 (&digests)[N_STAGES], u32 r,
+                                               const CuWave& w, const CuArgs& a) {
   u32 dig[N_STAGES];
 #pragma unroll
   for (u32 st = 0; st < N_STAGES; ++st) dig[st] = digests[st];
-  if (gwave == inj_wave && r == inj_round) {
+  if (w.gwave == a.inj_wave && r == a.inj_round) {
 #pragma unroll
     for (u32 st = 0; st < N_STAGES; ++st)
-      if (st == inj_stage) dig[st] ^= inj_mask;
+      if (st == a.inj_stage) dig[st] ^= a.inj_mask;
   }
-  if (lane == 0) {
+  if (w.lane == 0) {
 #pragma unroll
     for (u32 st = 0; st < N_STAGES; ++st) {
-      u32 want = expected[r * N_STAGES + st];
+      u32 want = a.expected[r * N_STAGES + st];
       if (dig[st] != want)
-        log_mismatch(res, max_records, gwave, hw, r, st, want, dig[st]);
-      if (dump != nullptr)
-        dump[((size_t)gwave * rounds + r) * N_STAGES + st] = dig[st];
+        log_mismatch(a.res, a.max_records, w.gwave, w.hw, r, st, want, dig[st]);
+      if (a.dump != nullptr)
+        a.dump[((size_t)w.gwave * a.rounds + r) * N_STAGES + st] = dig[st];
     }
   }
 }
@@ -167,11 +187,10 @@ typedef std::tuple<int64_t, int64_t, int64_t, std::vector<CuRecord>,
                    std::vector<int64_t>, double> CucheckOut;
 typedef std::tuple<int64_t, int64_t, int64_t, int64_t> CuInject;
 
-// What a launch needs besides the table, after the argument checks.
+// What a launch needs, after the argument checks; `res` owns args.res.
 struct CuLaunch {
   int64_t blocks;
-  u32* dump;
-  u32 inj_wave, inj_round, inj_stage, inj_mask;
+  CuArgs args;
   at::Tensor res;
 };
 
@@ -204,7 +223,9 @@ static inline CuLaunch cu_prepare(const char* who, const at::Tensor& expected,
   TORCH_CHECK(l.blocks >= 1 && l.blocks <= MAX_BLOCKS, who, ": default grid ", l.blocks,
               " out of range");
 
-  l.dump = nullptr;
+  CuArgs& a = l.args;  // no dump, no injection; res is set last
+  a = {(u32)seed_arg, (u32)rounds, (const u32*)expected.data_ptr(), nullptr,
+       (int)max_records, nullptr, NO_INJECT, 0, 0, 0};
   if (dump.has_value()) {
     const at::Tensor& d = *dump;
     TORCH_CHECK(d.is_cuda() && d.get_device() == expected.get_device(), who,
@@ -214,26 +235,25 @@ static inline CuLaunch cu_prepare(const char* who, const at::Tensor& expected,
     TORCH_CHECK(d.numel() == l.blocks * CU_WAVES * rounds * N_STAGES, who,
                 ": dump must hold ", l.blocks * CU_WAVES * rounds * N_STAGES,
                 " elements (waves x rounds x 4), got ", d.numel());
-    l.dump = (u32*)d.data_ptr();
+    a.dump = (u32*)d.data_ptr();
   }
 
-  l.inj_wave = NO_INJECT;
-  l.inj_round = l.inj_stage = l.inj_mask = 0;
   if (inject.has_value()) {
     int64_t w = std::get<0>(*inject), r = std::get<1>(*inject);
     int64_t s = std::get<2>(*inject), m = std::get<3>(*inject);
     TORCH_CHECK(w >= 0 && w < l.blocks * CU_WAVES && r >= 0 && r < rounds && s >= 0 &&
                     s < N_STAGES && m >= 0 && m <= 0xFFFFFFFFLL,
                 who, ": inject (wave, round, stage, mask) out of range");
-    l.inj_wave = (u32)w;
-    l.inj_round = (u32)r;
-    l.inj_stage = (u32)s;
-    l.inj_mask = (u32)m;
+    a.inj_wave = (u32)w;
+    a.inj_round = (u32)r;
+    a.inj_stage = (u32)s;
+    a.inj_mask = (u32)m;
   }
 
   l.res = at::zeros({RES_RECORDS + RECORD_WORDS * max_records},
                     expected.options().dtype(at::kInt));
   l.res.select(0, RES_FIRST).fill_(-1);  // u32 max: identity for atomicMin
+  a.res = (u32*)l.res.data_ptr();
   return l;
 }
 
@@ -259,13 +279,12 @@ static inline CucheckOut cu_read_result(const at::Tensor& res, int64_t max_recor
 }
 
 // One timed launch of a digest kernel on the current stream, after
-// cu_prepare and under the caller's device guard: `args` are the
-// kernel's own.  The events are destroyed before either error is
-// raised.
-template <typename Kernel, typename... Args>
+// cu_prepare and under the caller's device guard: the kernel gets l's
+// argument block, then `extras`, its own.  The events are destroyed
+// before either error is raised.
+template <typename Kernel, typename... Extras>
 static inline CucheckOut cu_launch_timed(Kernel kernel, const CuLaunch& l,
-                                         int64_t lds_bytes, int64_t max_records,
-                                         Args... args) {
+                                         int64_t lds_bytes, Extras... extras) {
   // more than 64 KiB of dynamic LDS has to be asked for; a kernel that
   // never touches it asks only to keep a second workgroup off the CU
   C10_HIP_CHECK(hipFuncSetAttribute((const void*)kernel,
@@ -277,7 +296,7 @@ static inline CucheckOut cu_launch_timed(Kernel kernel, const CuLaunch& l,
   C10_HIP_CHECK(hipEventCreate(&t1));
   C10_HIP_CHECK(hipEventRecord(t0, stream));
   hipLaunchKernelGGL(kernel, dim3((unsigned)l.blocks), dim3(CU_BLOCK), (size_t)lds_bytes,
-                     stream, args...);
+                     stream, l.args, extras...);
   hipError_t launch_err = hipGetLastError();
   (void)hipEventRecord(t1, stream);
   hipError_t sync_err = hipEventSynchronize(t1);
@@ -287,11 +306,11 @@ static inline CucheckOut cu_launch_timed(Kernel kernel, const CuLaunch& l,
   (void)hipEventDestroy(t1);
   C10_HIP_CHECK(launch_err);
   C10_HIP_CHECK(sync_err);
-  return cu_read_result(l.res, max_records, (double)ms / 1e3);
+  return cu_read_result(l.res, l.args.max_records, (double)ms / 1e3);
 }
 
-// Argument checks of the single-wave launchers (cucheck_values,
-// mxcheck_tile, fpcheck_values).
+// Argument checks of the single-wave launchers (<name>_values,
+// mxcheck_tile).
 static inline void cu_check_wave_args(const char* who, int64_t seed_arg, int64_t stage,
                                       int64_t round) {
   TORCH_CHECK(seed_arg >= 0 && seed_arg <= 0xFFFFFFFFLL, who, ": seed must be a u32");
@@ -299,4 +318,22 @@ static inline void cu_check_wave_args(const char* who, int64_t seed_arg, int64_t
               ", got ", stage);
   TORCH_CHECK(round >= 0 && round < MAX_ROUNDS, who, ": round must be in 0..",
               MAX_ROUNDS - 1, ", got ", round);
+}
+
+// The launch of a single-wave launcher, after its argument checks: one
+// workgroup of `block_threads` on the current stream with the kernel's
+// `args`, waited for; returns `out`, which the kernel has filled.
+template <typename Kernel, typename... Args>
+static inline at::Tensor cu_launch_values(Kernel kernel, int block_threads,
+                                          int64_t lds_bytes, at::Tensor out, Args... args) {
+  if (lds_bytes > 64 * 1024)  // more than that has to be asked for
+    C10_HIP_CHECK(hipFuncSetAttribute((const void*)kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds_bytes));
+  auto stream = at::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(block_threads), (size_t)lds_bytes, stream,
+                     args...);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  C10_HIP_CHECK(hipStreamSynchronize(stream));
+  return out;
 }

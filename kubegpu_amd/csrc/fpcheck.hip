@@ -415,26 +415,22 @@ __device__ __forceinline__ void fp_stage_cvt(u32 base, u32 rp, u32 lane, SINK& s
 }
 
 __global__ void __launch_bounds__(CU_BLOCK)
-fpcheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
-               u32* __restrict__ res, int max_records, u32* __restrict__ dump,
-               u32 inj_wave, u32 inj_round, u32 inj_stage, u32 inj_mask) {
+fpcheck_kernel(CuArgs a) {
 #if __HIP_DEVICE_COMPILE__
 #pragma clang fp contract(off)
-  const int lane = threadIdx.x % WAVE;
-  const u32 gwave = blockIdx.x * CU_WAVES + threadIdx.x / WAVE;
-  const u32 hw = cu_locate_wave(res, lane);
+  const CuWave w = cu_wave(a);
+  const u32 lane = (u32)w.lane;
 
-  for (u32 r = 0; r < rounds; ++r) {
+  for (u32 r = 0; r < a.rounds; ++r) {
     const u32 rp = r % FP_PERIOD;
     FpFold f0, f1, f2, f3;
-    fp_stage_f32(cu_base(seed, FP_STAGE0 + 0, rp), rp, (u32)lane, f0);
-    fp_stage_f64(cu_base(seed, FP_STAGE0 + 1, rp), rp, (u32)lane, f1);
-    fp_stage_packed(cu_base(seed, FP_STAGE0 + 2, rp), rp, (u32)lane, f2);
-    fp_stage_cvt(cu_base(seed, FP_STAGE0 + 3, rp), rp, (u32)lane, f3);
+    fp_stage_f32(cu_base(a.seed, FP_STAGE0 + 0, rp), rp, lane, f0);
+    fp_stage_f64(cu_base(a.seed, FP_STAGE0 + 1, rp), rp, lane, f1);
+    fp_stage_packed(cu_base(a.seed, FP_STAGE0 + 2, rp), rp, lane, f2);
+    fp_stage_cvt(cu_base(a.seed, FP_STAGE0 + 3, rp), rp, lane, f3);
     u32 dig[N_STAGES] = {wave_sum(f0.d), wave_sum(f1.d), wave_sum(f2.d), wave_sum(f3.d)};
 
-    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
-                   inj_wave, inj_round, inj_stage, inj_mask);
+    cu_check_round(dig, r, w, a);
   }
 #endif
 }
@@ -474,11 +470,7 @@ CucheckOut fpcheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
   CuLaunch l = cu_prepare("fpcheck", expected, seed_arg, rounds, blocks_arg,
                           max_records, dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
-
-  return cu_launch_timed(fpcheck_kernel, l, MAX_LDS_BYTES, max_records, (u32)seed_arg,
-                         (u32)rounds, (const u32*)expected.data_ptr(),
-                         (u32*)l.res.data_ptr(), (int)max_records, l.dump, l.inj_wave,
-                         l.inj_round, l.inj_stage, l.inj_mask);
+  return cu_launch_timed(fpcheck_kernel, l, MAX_LDS_BYTES);
 }
 
 // The raw result bits of one stage and round as an int64 tensor on the
@@ -487,12 +479,8 @@ at::Tensor fpcheck_values(int64_t seed_arg, int64_t stage, int64_t round) {
   cu_check_wave_args("fpcheck", seed_arg, stage, round);
   at::Tensor out = at::zeros({(int64_t)FP_OPS[stage] * FP_SLOTS[stage]},
                              at::TensorOptions().dtype(at::kLong).device(at::kCUDA));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(fpcheck_values_kernel, dim3(1), dim3(CU_BLOCK), 0, stream,
-                     (u32)seed_arg, (u32)stage, (u32)round, (u64*)out.data_ptr());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  C10_HIP_CHECK(hipStreamSynchronize(stream));
-  return out;
+  return cu_launch_values(fpcheck_values_kernel, CU_BLOCK, 0, out, (u32)seed_arg,
+                          (u32)stage, (u32)round, (u64*)out.data_ptr());
 }
 
 // Called from gpuprobe.hip's PYBIND11_MODULE; GIL released like the

@@ -324,26 +324,22 @@ LC_DEV u32 lc_stage_scan(u32 base, u32 lane, SINK& sink) {
 #endif  // __HIP_DEVICE_COMPILE__
 
 __global__ void __launch_bounds__(CU_BLOCK)
-lanecheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
-                 u32* __restrict__ res, int max_records, u32* __restrict__ dump,
-                 u32 inj_wave, u32 inj_round, u32 inj_stage, u32 inj_mask) {
+lanecheck_kernel(CuArgs a) {
 #if __HIP_DEVICE_COMPILE__
-  const int lane = threadIdx.x % WAVE;
-  const u32 gwave = blockIdx.x * CU_WAVES + threadIdx.x / WAVE;
-  const u32 hw = cu_locate_wave(res, lane);
-  const u32 base0 = cu_base(seed, LC_STAGE0 + 2, 0u);
+  const CuWave w = cu_wave(a);
+  const u32 lane = (u32)w.lane;
+  const u32 base0 = cu_base(a.seed, LC_STAGE0 + 2, 0u);
 
-  for (u32 r = 0; r < rounds; ++r) {
+  for (u32 r = 0; r < a.rounds; ++r) {
     const u32 rp = r % LC_PERIOD;
     LcFold f0, f1, f2, f3;
-    lc_stage_dpp(cu_base(seed, LC_STAGE0 + 0, rp), (u32)lane, f0);
-    lc_stage_xbar(cu_base(seed, LC_STAGE0 + 1, rp), (u32)lane, f1);
-    lc_stage_sgpr(cu_base(seed, LC_STAGE0 + 2, rp), base0, rp, (u32)lane, f2);
-    lc_stage_scan(cu_base(seed, LC_STAGE0 + 3, rp), (u32)lane, f3);
+    lc_stage_dpp(cu_base(a.seed, LC_STAGE0 + 0, rp), lane, f0);
+    lc_stage_xbar(cu_base(a.seed, LC_STAGE0 + 1, rp), lane, f1);
+    lc_stage_sgpr(cu_base(a.seed, LC_STAGE0 + 2, rp), base0, rp, lane, f2);
+    lc_stage_scan(cu_base(a.seed, LC_STAGE0 + 3, rp), lane, f3);
     u32 dig[N_STAGES] = {wave_sum(f0.d), wave_sum(f1.d), wave_sum(f2.d), wave_sum(f3.d)};
 
-    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
-                   inj_wave, inj_round, inj_stage, inj_mask);
+    cu_check_round(dig, r, w, a);
   }
 #endif
 }
@@ -376,10 +372,7 @@ CucheckOut lanecheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
   CuLaunch l = cu_prepare("lanecheck", expected, seed_arg, rounds, blocks_arg, max_records,
                           dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
-  return cu_launch_timed(lanecheck_kernel, l, MAX_LDS_BYTES, max_records, (u32)seed_arg,
-                         (u32)rounds, (const u32*)expected.data_ptr(),
-                         (u32*)l.res.data_ptr(), (int)max_records, l.dump, l.inj_wave,
-                         l.inj_round, l.inj_stage, l.inj_mask);
+  return cu_launch_timed(lanecheck_kernel, l, MAX_LDS_BYTES);
 }
 
 // What one wave folds for one stage and round as an int32 tensor on the
@@ -389,12 +382,8 @@ at::Tensor lanecheck_values(int64_t seed_arg, int64_t stage, int64_t round) {
   cu_check_wave_args("lanecheck", seed_arg, stage, round);
   at::Tensor out = at::zeros({(int64_t)(64 * LC_VALUE_SLOTS + 1)},
                              at::TensorOptions().dtype(at::kInt).device(at::kCUDA));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(lanecheck_values_kernel, dim3(1), dim3(WAVE), 0, stream, (u32)seed_arg,
-                     (u32)stage, (u32)round, (u32*)out.data_ptr());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  C10_HIP_CHECK(hipStreamSynchronize(stream));
-  return out;
+  return cu_launch_values(lanecheck_values_kernel, WAVE, 0, out, (u32)seed_arg, (u32)stage,
+                          (u32)round, (u32*)out.data_ptr());
 }
 
 typedef std::tuple<int64_t, int64_t, int64_t, int64_t> LcDppRow;

@@ -39,6 +39,49 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // 2 e2m3, 3 e3m2, 4 e2m1
 #define FMT_E2M1 4
 
+// C/D map of the f64 MFMA: lane l, register g holds row (l>>4) + 4g,
+// column l&15 (not the f32 16x16 map).  Row-major index of that element.
+__device__ __forceinline__ u32 mx_f64_index(int g, int lane) {
+  return 16 * ((lane >> 4) + 4 * g) + (lane & 15);
+}
+
+// Where a stage's accumulator tile goes, as in cucheck.hip: mxcheck_kernel
+// folds it into the digest, mxcheck_tile_kernel stores it; both run the
+// same stage code and go through the same two C/D maps.
+struct MxFold {
+  u32 dig = 0;
+  // 32x32 f32 tile in units of 1/unit -> exact integers, cucheck's fold
+  __device__ __forceinline__ void tile(f32x16 acc, float unit, int lane) {
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] *= unit;  // power of two: exact
+    dig = fold_tile(acc, lane);
+  }
+  // 16x16 f64 tile: both halves of the two's-complement int64
+  __device__ __forceinline__ void tile_f64(const f64x4& acc, int lane) {
+    u32 d = 0;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      u32 n = mx_f64_index(g, lane);
+      long long c = (long long)acc[g];
+      d += cu_fmix32((u32)c + cu_salt(n)) + cu_fmix32((u32)(c >> 32) + cu_salt(256u + n));
+    }
+    dig = wave_sum(d);
+  }
+};
+
+// Row-major as f64, in the stage's unit.
+struct MxDump {
+  double* out;
+  __device__ __forceinline__ void tile(const f32x16& acc, float unit, int lane) {
+#pragma unroll
+    for (int g = 0; g < 16; ++g) out[cu_tile_index(g, lane)] = (double)(acc[g] * unit);
+  }
+  __device__ __forceinline__ void tile_f64(const f64x4& acc, int lane) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) out[mx_f64_index(g, lane)] = acc[g];
+  }
+};
+
 // In all 32x32 stages lane l owns row rc = l&31 of A and column rc of B.
 // The k a fragment slot stands for is the same for A and B, and C = A*B
 // does not change under a permutation of k applied to both, so only the
@@ -48,7 +91,9 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // stage 0: f16.  Step s, half h: k = 16s + 8h + j, j = 0..7, two k per
 // word.  A is the sign-extended low 11 bits of a 16-bit half (the whole
 // f16 significand), B the low 5 bits.
-__device__ __forceinline__ f32x16 mx_stage_f16(u32 base, u32 rc, u32 half) {
+template <typename SINK>
+__device__ __forceinline__ void mx_stage_f16(u32 base, u32 rc, u32 half, int lane,
+                                             SINK& sink) {
   f32x16 acc = {0.f};
 #pragma unroll
   for (u32 s = 0; s < 8; ++s) {
@@ -64,7 +109,7 @@ __device__ __forceinline__ f32x16 mx_stage_f16(u32 base, u32 rc, u32 half) {
     }
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
   }
-  return acc;
+  sink.tile(acc, 1.f, lane);
 }
 
 // stage 1: OCP fp8.  Step s, half h: k = 16s + 8h + j, j = 0..7, one byte
@@ -78,7 +123,10 @@ __device__ __forceinline__ u32 mx_e5m2_codes(u32 w) {
   return (w & 0x83838383u) | ((0x0F0F0F0Fu + ((w >> 2) & 0x03030303u)) << 2);
 }
 
-__device__ __forceinline__ f32x16 mx_stage_fp8(u32 base, u32 rc, u32 half) {
+// The tile is in units of 1/32.
+template <typename SINK>
+__device__ __forceinline__ void mx_stage_fp8(u32 base, u32 rc, u32 half, int lane,
+                                             SINK& sink) {
   f32x16 acc = {0.f};
 #pragma unroll
   for (u32 s = 0; s < 8; ++s) {
@@ -91,7 +139,7 @@ __device__ __forceinline__ f32x16 mx_stage_fp8(u32 base, u32 rc, u32 half) {
         ((unsigned long long)mx_e5m2_codes(cu_fmix32(base + 1024u + w0 + 1u)) << 32);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_fp8_bf8((long)a, (long)b, acc, 0, 0, 0);
   }
-  return acc;
+  sink.tile(acc, 32.f, lane);
 }
 
 // stage 2: block-scaled e2m1.  A lane holds the 32 elements of row /
@@ -99,8 +147,11 @@ __device__ __forceinline__ f32x16 mx_stage_fp8(u32 base, u32 rc, u32 half) {
 // operand VGPRs (eight nibbles per word; the upper four VGPRs are not
 // read for this format), and byte 0 of its own scale VGPR (op_sel 0) is
 // the E8M0 scale of exactly those 32 elements.  Scales are 127 + two
-// bits of the row's / column's scale word, so 2^0 .. 2^3.
-__device__ __forceinline__ f32x16 mx_stage_mxfp4(u32 base, u32 rc, u32 half) {
+// bits of the row's / column's scale word, so 2^0 .. 2^3.  The tile is in
+// units of 1/4.
+template <typename SINK>
+__device__ __forceinline__ void mx_stage_mxfp4(u32 base, u32 rc, u32 half, int lane,
+                                               SINK& sink) {
   const u32 sa_word = cu_fmix32(base + 2048u + rc);
   const u32 sb_word = cu_fmix32(base + 2080u + rc);
   f32x16 acc = {0.f};
@@ -119,13 +170,14 @@ __device__ __forceinline__ f32x16 mx_stage_mxfp4(u32 base, u32 rc, u32 half) {
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, FMT_E2M1, FMT_E2M1,
                                                           0, sa, 0, sb);
   }
-  return acc;
+  sink.tile(acc, 4.f, lane);
 }
 
 // stage 3: f64, 16x16 tile.  Lane l holds A[l&15][4s + (l>>4)] and
 // B[4s + (l>>4)][l&15] of step s; operands are the sign-extended low 24
 // bits of a word.
-__device__ __forceinline__ f64x4 mx_stage_f64(u32 base, int lane) {
+template <typename SINK>
+__device__ __forceinline__ void mx_stage_f64(u32 base, int lane, SINK& sink) {
   const u32 rc = lane & 15, kq = lane >> 4;
   f64x4 acc = {0.0};
 #pragma unroll
@@ -135,58 +187,31 @@ __device__ __forceinline__ f64x4 mx_stage_f64(u32 base, int lane) {
     double b = (double)((int)(cu_fmix32(base + 512u + w) << 8) >> 8);
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
   }
-  return acc;
-}
-
-// 32x32 f32 tile in units of 1/unit -> exact integers, folded as cucheck
-// folds its tiles.
-__device__ __forceinline__ u32 mx_fold_scaled(f32x16 acc, float unit, int lane) {
-#pragma unroll
-  for (int g = 0; g < 16; ++g) acc[g] *= unit;  // power of two: exact
-  return fold_tile(acc, lane);
-}
-
-// Fold of the 16x16 f64 tile, both halves of the two's-complement int64.
-// C/D map of the f64 MFMA: lane l, register g holds row (l>>4) + 4g,
-// column l&15 (not the f32 16x16 map).
-__device__ __forceinline__ u32 mx_fold_f64(const f64x4& acc, int lane) {
-  u32 col = lane & 15, d = 0;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    u32 n = 16 * ((lane >> 4) + 4 * g) + col;
-    long long c = (long long)acc[g];
-    d += cu_fmix32((u32)c + cu_salt(n)) + cu_fmix32((u32)(c >> 32) + cu_salt(256u + n));
-  }
-  return wave_sum(d);
+  sink.tile_f64(acc, lane);
 }
 
 __global__ void __launch_bounds__(CU_BLOCK)
-mxcheck_kernel(u32 seed, u32 rounds, const u32* __restrict__ expected,
-               u32* __restrict__ res, int max_records, u32* __restrict__ dump,
-               u32 inj_wave, u32 inj_round, u32 inj_stage, u32 inj_mask) {
+mxcheck_kernel(CuArgs a) {
 #if __HIP_DEVICE_COMPILE__
-  const int lane = threadIdx.x % WAVE;
-  const u32 gwave = blockIdx.x * CU_WAVES + threadIdx.x / WAVE;
-  const u32 hw = cu_locate_wave(res, lane);
+  const CuWave w = cu_wave(a);
+  const int lane = w.lane;
   const u32 rc = lane & 31, half = lane >> 5;
 
-  for (u32 r = 0; r < rounds; ++r) {
-    u32 dig[N_STAGES];
-    dig[0] = fold_tile(mx_stage_f16(cu_base(seed, MX_STAGE0 + 0, r), rc, half), lane);
-    dig[1] = mx_fold_scaled(mx_stage_fp8(cu_base(seed, MX_STAGE0 + 1, r), rc, half),
-                            32.f, lane);
-    dig[2] = mx_fold_scaled(mx_stage_mxfp4(cu_base(seed, MX_STAGE0 + 2, r), rc, half),
-                            4.f, lane);
-    dig[3] = mx_fold_f64(mx_stage_f64(cu_base(seed, MX_STAGE0 + 3, r), lane), lane);
+  for (u32 r = 0; r < a.rounds; ++r) {
+    MxFold f0, f1, f2, f3;
+    mx_stage_f16(cu_base(a.seed, MX_STAGE0 + 0, r), rc, half, lane, f0);
+    mx_stage_fp8(cu_base(a.seed, MX_STAGE0 + 1, r), rc, half, lane, f1);
+    mx_stage_mxfp4(cu_base(a.seed, MX_STAGE0 + 2, r), rc, half, lane, f2);
+    mx_stage_f64(cu_base(a.seed, MX_STAGE0 + 3, r), lane, f3);
+    u32 dig[N_STAGES] = {f0.dig, f1.dig, f2.dig, f3.dig};
 
-    cu_check_round(dig, r, rounds, lane, gwave, hw, expected, res, max_records, dump,
-                   inj_wave, inj_round, inj_stage, inj_mask);
+    cu_check_round(dig, r, w, a);
   }
 #endif
 }
 
-// One workgroup; wave 0 writes the accumulator tile of one stage and
-// round row-major as f64, in the stage's unit (1, 1/32, 1/4, 1): 32x32
+// One workgroup; wave 0 runs one stage of one round and stores its
+// accumulator tile (MxDump) in the stage's unit (1, 1/32, 1/4, 1): 32x32
 // for stages 0-2, 16x16 for stage 3.  A digest cannot say which element
 // is wrong; this can.
 __global__ void __launch_bounds__(CU_BLOCK)
@@ -195,30 +220,16 @@ mxcheck_tile_kernel(u32 seed, u32 stage, u32 r, double* __restrict__ out) {
   if (threadIdx.x >= WAVE) return;
   const int lane = threadIdx.x;
   const u32 base = cu_base(seed, MX_STAGE0 + stage, r);
-  if (stage == 3) {
-    f64x4 acc = mx_stage_f64(base, lane);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) out[16 * ((lane >> 4) + 4 * g) + (lane & 15)] = acc[g];
-    return;
-  }
   const u32 rc = lane & 31, half = lane >> 5;
-  f32x16 acc;
-  float unit;
-  if (stage == 0) {
-    acc = mx_stage_f16(base, rc, half);
-    unit = 1.f;
-  } else if (stage == 1) {
-    acc = mx_stage_fp8(base, rc, half);
-    unit = 32.f;
-  } else {
-    acc = mx_stage_mxfp4(base, rc, half);
-    unit = 4.f;
-  }
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    u32 row = (g & 3) + 8 * (g >> 2) + 4 * half;
-    out[32 * row + rc] = (double)(acc[g] * unit);
-  }
+  MxDump sink{out};
+  if (stage == 0)
+    mx_stage_f16(base, rc, half, lane, sink);
+  else if (stage == 1)
+    mx_stage_fp8(base, rc, half, lane, sink);
+  else if (stage == 2)
+    mx_stage_mxfp4(base, rc, half, lane, sink);
+  else
+    mx_stage_f64(base, lane, sink);
 #endif
 }
 
@@ -231,11 +242,7 @@ CucheckOut mxcheck_run(at::Tensor expected, int64_t seed_arg, int64_t rounds,
   CuLaunch l = cu_prepare("mxcheck", expected, seed_arg, rounds, blocks_arg,
                           max_records, dump, inject);
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(expected));
-
-  return cu_launch_timed(mxcheck_kernel, l, MAX_LDS_BYTES, max_records, (u32)seed_arg,
-                         (u32)rounds, (const u32*)expected.data_ptr(),
-                         (u32*)l.res.data_ptr(), (int)max_records, l.dump, l.inj_wave,
-                         l.inj_round, l.inj_stage, l.inj_mask);
+  return cu_launch_timed(mxcheck_kernel, l, MAX_LDS_BYTES);
 }
 
 // The accumulator tile of one stage and round as a float64 tensor on the
@@ -244,12 +251,8 @@ at::Tensor mxcheck_tile(int64_t seed_arg, int64_t stage, int64_t round) {
   cu_check_wave_args("mxcheck", seed_arg, stage, round);
   int64_t n = stage == 3 ? 16 : 32;
   at::Tensor out = at::zeros({n, n}, at::TensorOptions().dtype(at::kDouble).device(at::kCUDA));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(mxcheck_tile_kernel, dim3(1), dim3(CU_BLOCK), 0, stream,
-                     (u32)seed_arg, (u32)stage, (u32)round, (double*)out.data_ptr());
-  C10_HIP_KERNEL_LAUNCH_CHECK();
-  C10_HIP_CHECK(hipStreamSynchronize(stream));
-  return out;
+  return cu_launch_values(mxcheck_tile_kernel, CU_BLOCK, 0, out, (u32)seed_arg, (u32)stage,
+                          (u32)round, (double*)out.data_ptr());
 }
 
 // Called from gpuprobe.hip's PYBIND11_MODULE; GIL released like the

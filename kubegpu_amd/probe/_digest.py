@@ -1,7 +1,8 @@
 """What the digest probes (cucheck, mxcheck, fpcheck, atomcheck, lanecheck)
-share on the host: the hash that generates their inputs, the result type, the
-decoding of the kernel's result block and the dump run.  Their kernels
-share csrc/cucheck_common.h the same way.
+share on the host: the hash that generates their inputs, the one-round and
+period helpers of their references, the result type, the run body, the
+decoding of the kernel's result block and of its value rows, and the dump
+run.  Their kernels share csrc/cucheck_common.h the same way.
 
 Imports neither torch nor numpy at import time.
 """
@@ -39,6 +40,26 @@ def _salt(n):
     import numpy as np
 
     return (n.astype(np.uint32) + np.uint32(1)) * np.uint32(0x9E3779B9)
+
+
+def one_round(name: str, r: int):
+    """Round ``r`` as the uint32[1] array the stage functions take."""
+    import numpy as np
+
+    r = int(r)
+    if not 0 <= r < 65536:
+        raise ValueError(f"{name}: round must be in 0..65535, got {r}")
+    return np.array([r], dtype=np.uint32)
+
+
+def tile_period(rows, rounds: int, period: int):
+    """The table of ``rounds`` rounds of a probe whose inputs repeat with
+    ``period``, from its first min(rounds, period) rows."""
+    import numpy as np
+
+    if rounds <= period:
+        return rows
+    return np.tile(rows, (-(-rounds // period), 1))[:rounds].copy()
 
 
 # -- GPU run ---------------------------------------------------------------------
@@ -157,6 +178,39 @@ def fill_result(res: DigestResult, raw, stages: Sequence[str], device,
         for name, f in zip(res.rate_fields(), work_per_wave_round):
             setattr(res, name, work * f)
     return res
+
+
+def run_probe(name: str, res: DigestResult, stages: Sequence[str],
+              work_per_wave_round: Sequence[int], unit: float, reference, seed: int,
+              blocks: int, max_records: int, device, inject, expected, *extra) -> DigestResult:
+    """The body of ``cucheck()``, ``mxcheck()``, ``fpcheck()`` and
+    ``lanecheck()``: ``res.rounds`` rounds of ``<name>_run`` against the
+    table ``expected``, or ``reference()`` where that is None, into
+    ``res``.  ``extra`` goes between ``blocks`` and ``max_records``."""
+    from ._active import _ext
+
+    ext = _ext()
+    device = _device(device)
+    rounds = res.rounds
+    if not 1 <= rounds <= 65536:
+        raise ValueError(f"{name}: rounds must be in 1..65536, got {rounds}")
+    table = expected if expected is not None else reference()
+    tensor = expected_tensor(name, table, rounds, stages, device)
+    inject = None if inject is None else tuple(int(x) for x in inject)
+    raw = getattr(ext, name + "_run")(
+        tensor, seed, rounds, blocks, *extra, int(max_records), None, inject)
+    return fill_result(res, raw, stages, device, work_per_wave_round, unit)
+
+
+def value_rows(name: str, raw, names: Sequence[str], rows: int, stage: int) -> dict:
+    """{slot name: row of 64} from what ``<name>_values`` returned for
+    ``stage``, viewed as unsigned: ``rows`` rows of 64 lanes, then the
+    number of rows the kernel filled."""
+    if int(raw[-1]) != len(names):
+        raise RuntimeError(f"{name}: the kernel filled {int(raw[-1])} slots of stage "
+                           f"{stage}, the reference has {len(names)}")
+    table = raw[:-1].reshape(rows, 64)
+    return {n: table[k] for k, n in enumerate(names)}
 
 
 def wave_digests(name: str, run, table, stages: Sequence[str], seed: int, rounds: int,

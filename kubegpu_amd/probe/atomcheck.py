@@ -614,18 +614,13 @@ def _stage(seed: int, stage: int, r) -> _Stage:
     return st
 
 
-def _one_round(r: int):
-    import numpy as np
-
-    r = int(r)
-    if not 0 <= r < 65536:
-        raise ValueError(f"atomcheck: round must be in 0..65535, got {r}")
-    return np.array([r], dtype=np.uint32)
+def _round_stage(seed: int, stage: int, r: int) -> _Stage:
+    return _stage(int(seed) & _M32, int(stage), _shared.one_round("atomcheck", r))
 
 
 def slot_table(stage: int) -> List[Tuple[str, str]]:
     """(name, kind) of every result slot of a stage, in slot order."""
-    return [(s.name, s.kind) for s in _stage(0, int(stage), _one_round(0)).slots]
+    return [(s.name, s.kind) for s in _round_stage(0, stage, 0).slots]
 
 
 def reference_values(seed: int, stage: int, r: int):
@@ -635,7 +630,7 @@ def reference_values(seed: int, stage: int, r: int):
     arrivals in lane order and is defined only as a multiset per cell
     l & 7 (for ``xchg`` together with the cell's final); "final" rows
     hold cells 0..7, the rest is zero."""
-    st = _stage(int(seed) & _M32, int(stage), _one_round(r))
+    st = _round_stage(seed, stage, r)
     return {s.name: s.values[0] for s in st.slots}
 
 
@@ -645,7 +640,7 @@ def reference_contended(seed: int, stage: int, r: int):
     [8] or None for the op's identity, operand per lane [64]); lane l
     acts on cell l & 7.  Integer types carry uint64 patterns, float
     types signed integers."""
-    st = _stage(int(seed) & _M32, int(stage), _one_round(r))
+    st = _round_stage(seed, stage, r)
     return [(n, op, t, None if init is None else init[0], x[0])
             for n, op, t, init, x in st.contended]
 
@@ -653,7 +648,7 @@ def reference_contended(seed: int, stage: int, r: int):
 def reference_cross(seed: int, r: int):
     """The cross-wave phase's inputs for one round: (initial values
     uint64[64], [(cell, op, operand) for every lane of every wave])."""
-    st = _stage(int(seed) & _M32, 0, _one_round(r))
+    st = _round_stage(seed, 0, r)
     init, contributions = st.cross
     flat = []
     for target, op, x in contributions:
@@ -702,9 +697,7 @@ def reference_digests(seed: int, rounds: int):
     if n:
         for s in range(len(STAGES)):
             rows[:, s] = _digest(_stage(seed, s, r))
-    if rounds <= PERIOD:
-        return rows
-    return np.tile(rows, (-(-rounds // PERIOD), 1))[:rounds].copy()
+    return _shared.tile_period(rows, rounds, PERIOD)
 
 
 # -- the shared region ------------------------------------------------------------------
@@ -972,12 +965,7 @@ def wave_values(seed: int, stage: int, r: int, device=None):
     names = [n for n, _ in slot_table(stage)]
     with torch.cuda.device(_device(device)):
         raw = _ext().atomcheck_values(int(seed), stage, int(r)).cpu().numpy()
-    raw = raw.view(np.uint64)
-    if int(raw[-1]) != len(names):
-        raise RuntimeError(f"atomcheck: the kernel filled {int(raw[-1])} slots of stage "
-                           f"{stage}, the reference has {len(names)}")
-    rows = raw[:-1].reshape(_VALUE_ROWS, 64)
-    return {name: rows[k] for k, name in enumerate(names)}
+    return _shared.value_rows("atomcheck", raw.view(np.uint64), names, _VALUE_ROWS, stage)
 
 
 # -- child process -----------------------------------------------------------

@@ -154,9 +154,7 @@ def _matmul_digests(seed: int, stage: int, r):
     bt = _signed_bytes(_words(seed, stage, r, 32 * wpr, 32 * wpr)).reshape(n, 32, 4 * wpr)
     # |C| <= 2**22: float64 products and sums are exact, and BLAS is fast
     c = np.matmul(a.astype(np.float64), bt.astype(np.float64).transpose(0, 2, 1))
-    cu = (c.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).reshape(n, 1024)
-    salt = _salt(np.arange(1024, dtype=np.uint32))  # 32*i + j, row-major
-    return _fmix32(cu + salt[None, :]).sum(axis=1, dtype=np.uint32)
+    return fold_values(stage, c)
 
 
 def _valu_digests(seed: int, r):
@@ -309,22 +307,14 @@ def cucheck(
     CU."""
     rounds, blocks, lds_bytes = int(rounds), int(blocks), int(lds_bytes)
     seed = int(seed)
-    ext = _ext()
-    device = _device(device)
-    if not 1 <= rounds <= 65536:
-        raise ValueError(f"cucheck: rounds must be in 1..65536, got {rounds}")
     if lds_bytes < 4096 or lds_bytes > DEFAULT_LDS_BYTES or lds_bytes % 4096:
         raise ValueError(
             f"cucheck: lds_bytes must be a multiple of 4096 in 4096..163840, got {lds_bytes}")
-    table = _expected if _expected is not None else reference_digests(
-        seed, rounds, lds_bytes // 64)
-    expected = _digest.expected_tensor("cucheck", table, rounds, STAGES, device)
-    inject = None if _inject is None else tuple(int(x) for x in _inject)
-    raw = ext.cucheck_run(
-        expected, seed, rounds, blocks, lds_bytes, int(max_records), None, inject)
-    return _digest.fill_result(
-        CucheckResult(rounds=rounds), raw, STAGES, device,
-        (_I8_OPS_PER_WAVE_ROUND, _BF16_FLOPS_PER_WAVE_ROUND), 1e12)
+    return _digest.run_probe(
+        "cucheck", CucheckResult(rounds=rounds), STAGES,
+        (_I8_OPS_PER_WAVE_ROUND, _BF16_FLOPS_PER_WAVE_ROUND), 1e12,
+        lambda: reference_digests(seed, rounds, lds_bytes // 64),
+        seed, blocks, max_records, device, _inject, _expected, lds_bytes)
 
 
 def wave_digests(seed: int, rounds: int, blocks: int = 0,

@@ -627,27 +627,20 @@ def _stage(seed: int, stage: int, r):
     return ops, dict(zip(OPS[stage], res))
 
 
-def _one_round(r: int):
-    import numpy as np
-
-    r = int(r)
-    if not 0 <= r < 65536:
-        raise ValueError(f"fpcheck: round must be in 0..65535, got {r}")
-    return np.array([r], dtype=np.uint32)
-
-
 def reference_values(seed: int, stage: int, r: int):
     """Raw result bits of one stage and round: {operation: uint64[slots]}
     in OPS[stage] order, slot q = 64 j + lane.  NaN results are canonical.
     Raises RuntimeError if this host flushes subnormals."""
-    _, res = _stage(int(seed) & 0xFFFFFFFF, int(stage), _one_round(r))
+    _, res = _stage(int(seed) & 0xFFFFFFFF, int(stage),
+                      _shared.one_round("fpcheck", r))
     return {k: v[0] for k, v in res.items()}
 
 
 def reference_operands(seed: int, stage: int, r: int):
     """The operand bit patterns behind ``reference_values``:
     {name: uint64[slots]}."""
-    ops, _ = _stage(int(seed) & 0xFFFFFFFF, int(stage), _one_round(r))
+    ops, _ = _stage(int(seed) & 0xFFFFFFFF, int(stage),
+                      _shared.one_round("fpcheck", r))
     return {k: v[0] for k, v in ops.items()}
 
 
@@ -704,9 +697,7 @@ def reference_digests(seed: int, rounds: int):
             r = np.arange(lo, min(lo + 32, n), dtype=np.uint32)
             for s in range(len(STAGES)):
                 rows[lo:lo + len(r), s] = _digest(s, _stage(seed, s, r)[1])
-    if rounds <= PERIOD:
-        return rows
-    return np.tile(rows, (-(-rounds // PERIOD), 1))[:rounds].copy()
+    return _shared.tile_period(rows, rounds, PERIOD)
 
 
 # -- GPU run ---------------------------------------------------------------------
@@ -744,16 +735,10 @@ def fpcheck(
     reference table; both are test hooks, since a test cannot corrupt a
     rounding unit."""
     rounds, blocks, seed = int(rounds), int(blocks), int(seed)
-    ext = _ext()
-    device = _device(device)
-    if not 1 <= rounds <= 65536:
-        raise ValueError(f"fpcheck: rounds must be in 1..65536, got {rounds}")
-    table = _expected if _expected is not None else reference_digests(seed, rounds)
-    expected = _shared.expected_tensor("fpcheck", table, rounds, STAGES, device)
-    inject = None if _inject is None else tuple(int(x) for x in _inject)
-    raw = ext.fpcheck_run(expected, seed, rounds, blocks, int(max_records), None, inject)
-    return _shared.fill_result(
-        FpcheckResult(rounds=rounds), raw, STAGES, device, _OPS_PER_WAVE_ROUND, 1e9)
+    return _shared.run_probe(
+        "fpcheck", FpcheckResult(rounds=rounds), STAGES, _OPS_PER_WAVE_ROUND, 1e9,
+        lambda: reference_digests(seed, rounds), seed, blocks, max_records, device,
+        _inject, _expected)
 
 
 def wave_digests(seed: int, rounds: int, blocks: int = 0, device=None):

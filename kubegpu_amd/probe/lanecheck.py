@@ -525,24 +525,16 @@ def _stage(seed: int, stage: int, r) -> List[tuple]:
     return _STAGE_FUNCS[stage](seed, r)
 
 
-def _one_round(r: int):
-    import numpy as np
-
-    r = int(r)
-    if not 0 <= r < 65536:
-        raise ValueError(f"lanecheck: round must be in 0..65535, got {r}")
-    return np.array([r], dtype=np.uint32)
-
-
 def slot_table(stage: int) -> List[str]:
     """The name of every result slot of a stage, in slot order."""
-    return [name for name, _ in _stage(0, int(stage), _one_round(0))]
+    return [name for name, _ in _stage(0, int(stage), _shared.one_round("lanecheck", 0))]
 
 
 def reference_values(seed: int, stage: int, r: int):
     """What a wave folds in one stage and round: {slot name: uint32[64]},
     in slot order, exact per lane."""
-    return {name: v[0] for name, v in _stage(int(seed) & _M32, int(stage), _one_round(r))}
+    slots = _stage(int(seed) & _M32, int(stage), _shared.one_round("lanecheck", r))
+    return {name: v[0] for name, v in slots}
 
 
 def digest_of(values) -> int:
@@ -591,9 +583,7 @@ def reference_digests(seed: int, rounds: int):
     if n:
         for s in range(len(STAGES)):
             rows[:, s] = _digest(_stage(seed, s, r))
-    if rounds <= PERIOD:
-        return rows
-    return np.tile(rows, (-(-rounds // PERIOD), 1))[:rounds].copy()
+    return _shared.tile_period(rows, rounds, PERIOD)
 
 
 # -- GPU run ---------------------------------------------------------------------
@@ -635,14 +625,10 @@ def lanecheck(
         raise ValueError(f"lanecheck: rounds must be in 1..65536, got {rounds}")
     if not 0 <= blocks <= 4096:
         raise ValueError(f"lanecheck: blocks must be in 0..4096, got {blocks}")
-    ext = _ext()
-    device = _device(device)
-    table = _expected if _expected is not None else reference_digests(seed, rounds)
-    expected = _shared.expected_tensor("lanecheck", table, rounds, STAGES, device)
-    inject = None if _inject is None else tuple(int(x) for x in _inject)
-    raw = ext.lanecheck_run(expected, seed, rounds, blocks, int(max_records), None, inject)
-    return _shared.fill_result(
-        LanecheckResult(rounds=rounds), raw, STAGES, device, _OPS_PER_WAVE_ROUND, 1e9)
+    return _shared.run_probe(
+        "lanecheck", LanecheckResult(rounds=rounds), STAGES, _OPS_PER_WAVE_ROUND, 1e9,
+        lambda: reference_digests(seed, rounds), seed, blocks, max_records, device,
+        _inject, _expected)
 
 
 def wave_digests(seed: int, rounds: int, blocks: int = 0, device=None):
@@ -664,12 +650,7 @@ def wave_values(seed: int, stage: int, r: int, device=None):
     names = slot_table(stage)
     with torch.cuda.device(_device(device)):
         raw = _ext().lanecheck_values(int(seed), stage, int(r)).cpu().numpy()
-    raw = raw.view(np.uint32)
-    if int(raw[-1]) != len(names):
-        raise RuntimeError(f"lanecheck: the kernel filled {int(raw[-1])} slots of stage "
-                           f"{stage}, the reference has {len(names)}")
-    rows = raw[:-1].reshape(_VALUE_ROWS, 64)
-    return {name: rows[k] for k, name in enumerate(names)}
+    return _shared.value_rows("lanecheck", raw.view(np.uint32), names, _VALUE_ROWS, stage)
 
 
 # -- child process -----------------------------------------------------------

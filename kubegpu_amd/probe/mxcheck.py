@@ -266,25 +266,38 @@ def matmul_tile(seed: int, stage: int, r: int):
     return a[0].astype(np.int64) @ bt[0].astype(np.int64).T
 
 
+def fold_tile(stage: int, tile):
+    """The uint32 digest of a stage's tile in the stage's unit
+    (``wave_tile`` or ``matmul_tile``), by the module docstring's
+    definition.  Leading axes are kept: tile[..., n, n] gives
+    digests[...]."""
+    import numpy as np
+
+    stage = int(stage)
+    if stage not in range(len(STAGES)):
+        raise ValueError(f"fold_tile: stage must be in 0..3, got {stage}")
+    tile, n = np.asarray(tile), TILE_DIMS[stage]
+    if tile.shape[-2:] != (n, n):
+        raise ValueError(f"fold_tile: stage {stage} takes [..., {n}, {n}], got {tile.shape}")
+    c = tile.astype(np.int64).reshape(tile.shape[:-2] + (n * n,))
+    idx = np.arange(n * n, dtype=np.uint32)  # n*i + j, row-major
+    with np.errstate(over="ignore"):
+        h = _fmix32((c & 0xFFFFFFFF).astype(np.uint32) + _salt(idx))
+        if stage == 3:
+            hi = ((c >> 32) & 0xFFFFFFFF).astype(np.uint32)
+            return (h.sum(axis=-1, dtype=np.uint32)
+                    + _fmix32(hi + _salt(idx + np.uint32(256))).sum(axis=-1, dtype=np.uint32))
+        return h.sum(axis=-1, dtype=np.uint32)
+
+
 def _digests(seed: int, stage: int, r):
     import numpy as np
 
     a, bt = operands(seed, stage, r)
-    n = len(r)
     # every partial sum is an integer below 2**24 in stages 0-2 (float32)
     # and below 2**53 in stage 3 (float64): products and sums are exact
     # in any order, and BLAS is fast
-    c = np.matmul(a, bt.transpose(0, 2, 1)).astype(np.int64)
-    if stage == 3:
-        c = c.reshape(n, 256)
-        lo = (c & 0xFFFFFFFF).astype(np.uint32)
-        hi = ((c >> 32) & 0xFFFFFFFF).astype(np.uint32)
-        idx = np.arange(256, dtype=np.uint32)
-        return (_fmix32(lo + _salt(idx)[None, :]).sum(axis=1, dtype=np.uint32)
-                + _fmix32(hi + _salt(idx + np.uint32(256))[None, :]).sum(axis=1, dtype=np.uint32))
-    cu = (c & 0xFFFFFFFF).astype(np.uint32).reshape(n, 1024)
-    salt = _salt(np.arange(1024, dtype=np.uint32))  # 32*i + j, row-major
-    return _fmix32(cu + salt[None, :]).sum(axis=1, dtype=np.uint32)
+    return fold_tile(stage, np.matmul(a, bt.transpose(0, 2, 1)))
 
 
 def reference_digests(seed: int, rounds: int):
@@ -341,16 +354,10 @@ def mxcheck(
     reference table; both are test hooks, since a test cannot corrupt a
     matrix core."""
     rounds, blocks, seed = int(rounds), int(blocks), int(seed)
-    ext = _ext()
-    device = _device(device)
-    if not 1 <= rounds <= 65536:
-        raise ValueError(f"mxcheck: rounds must be in 1..65536, got {rounds}")
-    table = _expected if _expected is not None else reference_digests(seed, rounds)
-    expected = _digest.expected_tensor("mxcheck", table, rounds, STAGES, device)
-    inject = None if _inject is None else tuple(int(x) for x in _inject)
-    raw = ext.mxcheck_run(expected, seed, rounds, blocks, int(max_records), None, inject)
-    return _digest.fill_result(
-        MxcheckResult(rounds=rounds), raw, STAGES, device, _FLOPS_PER_WAVE_ROUND, 1e12)
+    return _digest.run_probe(
+        "mxcheck", MxcheckResult(rounds=rounds), STAGES, _FLOPS_PER_WAVE_ROUND, 1e12,
+        lambda: reference_digests(seed, rounds), seed, blocks, max_records, device,
+        _inject, _expected)
 
 
 def wave_digests(seed: int, rounds: int, blocks: int = 0, device=None):

@@ -227,6 +227,20 @@ def test_reference_digests_fold_the_tiles():
         assert ref[r].tolist() == _digest_of_tiles(0xDEADBEEF, r)
 
 
+@pytest.mark.parametrize("seed,r", [(0, 0), (0xDEADBEEF, 1)])
+def test_fold_tile_of_the_exact_product_is_the_reference_digest(seed, r):
+    ref = mx.reference_digests(seed, r + 1)
+    for stage in range(4):
+        tile = mx.matmul_tile(seed, stage, r)
+        assert int(mx.fold_tile(stage, tile)) == int(ref[r, stage])
+        # leading axes are kept
+        assert mx.fold_tile(stage, np.stack([tile, tile])).tolist() == [int(ref[r, stage])] * 2
+    with pytest.raises(ValueError):
+        mx.fold_tile(4, np.zeros((32, 32), dtype=np.int64))
+    with pytest.raises(ValueError):
+        mx.fold_tile(3, np.zeros((32, 32), dtype=np.int64))
+
+
 def test_inputs_differ_from_cuchecks():
     from kubegpu_amd.probe import cucheck as cc
 

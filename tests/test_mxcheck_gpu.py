@@ -66,6 +66,18 @@ def test_wave_tile_equals_the_exact_product(stage, seed, r):
             f"transposed tile matches: {bool(np.array_equal(got.T, want))}")
 
 
+@pytest.mark.parametrize("seed,r", [(0, 0), (0xDEADBEEF, 1)])
+def test_dumped_tiles_fold_to_the_production_digests(seed, r):
+    """The tile dump and the kernel that runs in production are the same
+    stage code and the same two C/D maps: folding what one stores gives
+    what every wave of the other compares."""
+    got = mx.wave_digests(seed, rounds=2, blocks=1)
+    assert got.shape == (16, 2, 4)
+    for stage in range(4):
+        folded = int(mx.fold_tile(stage, mx.wave_tile(seed, stage, r)))
+        assert got[:, r, stage].tolist() == [folded] * 16, mx.STAGES[stage]
+
+
 # 2. every wave against the reference --------------------------------------------------
 
 @pytest.mark.parametrize("blocks,rounds", [(1, 1), (3, 3), (0, 2)])
