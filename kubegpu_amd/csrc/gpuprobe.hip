@@ -9,22 +9,40 @@
 // Kernel notes (per /opt/skills/guides/cdna_hip_programming.md):
 //  * 256-thread blocks = 4 wave64s; 16 B/lane vectorized access
 //    (uint4) -> 4 KiB per block per instruction.
-//  * grid-stride with >> 256 workgroups so all 8 XCDs / 256 CUs fill.
-//  * copy is the float4-copy pattern that measures ~79% of HBM peak.
+//  * read, fill and the copy variants 0..3 are grid-stride with >> 256
+//    workgroups so all 8 XCDs / 256 CUs fill.
+//  * copy() launches copy_kernel_tiles: one workgroup per contiguous
+//    tile, handed out in address order, with the number of workgroups
+//    resident per CU capped by an LDS request (see COPY_TILES_*); the
+//    float4-copy pattern at ~83% of HBM peak at 1 GiB.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
+#include <string>
 
 #define WAVE 64
 #define BLOCK 256
-// Measured on MI355X (gpurun copy sweep, 1 GiB buffers): 1024 blocks
-// (4 per CU) + nontemporal beats larger grids — 5816 vs 4533 GB/s at
-// 4096 blocks; NT avoids LLC pollution on pure streams.
+// Default grid of the grid-stride copy variants 0..3 (copy_variant,
+// copy_bw_gbps) and of read_sum; copy() launches the tile kernel.
+// Measured on MI355X (copy sweep, 1 GiB buffers): 1024 blocks (4 per
+// CU) + nontemporal beats larger grids of the same kernel — 5816 vs
+// 4533 GB/s at 4096 blocks; NT avoids LLC pollution on pure streams.
 #define DEFAULT_COPY_BLOCKS 1024
+// What copy() launches: copy_kernel_tiles<2> (8 KiB tiles, one per
+// workgroup) with at most 3 workgroups resident per CU.  Best median of
+// the U x resident sweep at 1 GiB, 50 launches x 3 rounds in one
+// process: 6,618 GB/s against 5,838 for the grid-stride kernel above
+// re-measured between the candidates (its max - min: 58); uncapped
+// U=2 gives 6,221, U=1 capped at 6 6,474.  64 MiB 6,602 vs 6,437,
+// 256 MiB 6,738 vs 6,344, 4 GiB 6,636 vs 5,604, 1 MiB (launch-bound)
+// 666 vs 673 within the spread — profiles/copy_tiles_sweep_mi355x.json.
+#define COPY_TILES_UNROLL 2
+#define COPY_TILES_RESIDENT 3
 // Pure write streams saturate earlier: >≈900 workgroups the write-drain
 // path contends and bandwidth collapses (measured: 640 wg 6,229 GB/s,
 // 1024 wg 4,300 GB/s at 1 GiB — profiles/write_bw_sweep_mi355x.json).
@@ -100,6 +118,43 @@ __global__ void copy_kernel_v4_mixed(const uint4v* __restrict__ src,
   for (; i < n4; i += stride) {
     uint4v v = src[i];
     __builtin_nontemporal_store(v, &dst[i]);
+  }
+}
+
+// Address-ordered tiles: tile t is the BLOCK*U consecutive vectors from
+// t*BLOCK*U, and the normal launch has one workgroup per tile, so the
+// dispatcher hands the buffer out in address order as workgroups retire
+// (a persistent grid-stride loop drifts apart instead).  A thread issues
+// its U loads back to back at lane stride BLOCK, so every wave
+// instruction still covers 1 KiB contiguous, then its U stores.  The
+// outer loop runs more than once only on a grid capped below the tile
+// count.  The kernel declares no LDS: what the launch asks for only
+// limits how many of these workgroups a CU holds (launch_copy_tiles).
+template <int U>
+__global__ void __launch_bounds__(BLOCK)
+copy_kernel_tiles(const uint4v* __restrict__ src, uint4v* __restrict__ dst, size_t n4) {
+  constexpr size_t T = (size_t)BLOCK * U;
+  const size_t tiles = (n4 + T - 1) / T;
+  for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const size_t base = t * T + threadIdx.x;
+    uint4v v[U];
+    if (t * T + T <= n4) {  // full tile (uniform over the workgroup): no compares
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        v[u] = __builtin_nontemporal_load(&src[base + (size_t)u * BLOCK]);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        __builtin_nontemporal_store(v[u], &dst[base + (size_t)u * BLOCK]);
+    } else {  // the last, partial tile
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (base + (size_t)u * BLOCK < n4)
+          v[u] = __builtin_nontemporal_load(&src[base + (size_t)u * BLOCK]);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (base + (size_t)u * BLOCK < n4)
+          __builtin_nontemporal_store(v[u], &dst[base + (size_t)u * BLOCK]);
+    }
   }
 }
 
@@ -221,6 +276,60 @@ static void launch_copy(const void* src, void* dst, size_t n4, int64_t variant,
                        (const uint4*)src, (uint4*)dst, n4);
 }
 
+// LDS of one CU, and the step that the hardware hands it out in.
+#define CU_LDS_BYTES (160 * 1024)
+#define LDS_GRANULE 1280
+#define MAX_DEVICES 64
+
+static void check_tiles_args(int64_t unroll, int64_t resident, int64_t max_blocks) {
+  TORCH_CHECK(unroll == 1 || unroll == 2 || unroll == 4 || unroll == 8,
+              "gpuprobe: unroll must be 1, 2, 4 or 8, got ", unroll);
+  TORCH_CHECK(resident >= 0 && resident <= 8, "gpuprobe: resident ", resident,
+              " out of range 0..8");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= MAX_BLOCKS,
+              "gpuprobe: max_blocks out of range 0..", MAX_BLOCKS);
+}
+
+template <int U>
+static void launch_copy_tiles_u(const void* src, void* dst, size_t n4, int resident,
+                                int max_blocks, hipStream_t stream) {
+  size_t tiles = (n4 + (size_t)BLOCK * U - 1) / ((size_t)BLOCK * U);
+  size_t cap = max_blocks > 0 ? (size_t)max_blocks : (size_t)MAX_BLOCKS;
+  // Residency cap: the kernel never touches this LDS.  A CU holds only
+  // as many workgroups as its 160 KiB cover, so asking for a 1/resident
+  // share of it (rounded down to whole granules) keeps a CU from taking
+  // more than `resident` of these workgroups while tiles are still
+  // handed out in order; resident == 0 asks for none and leaves the
+  // limit to the 32 waves per CU (8 workgroups).
+  size_t lds = resident > 0 ? CU_LDS_BYTES / resident / LDS_GRANULE * LDS_GRANULE : 0;
+  if (lds > 64 * 1024) {  // more than that has to be asked for, once per device
+    static std::atomic<bool> raised[MAX_DEVICES];
+    int dev = 0;
+    C10_HIP_CHECK(hipGetDevice(&dev));
+    TORCH_CHECK(dev >= 0 && dev < MAX_DEVICES, "gpuprobe: device index ", dev);
+    if (!raised[dev].load(std::memory_order_acquire)) {
+      C10_HIP_CHECK(hipFuncSetAttribute((const void*)copy_kernel_tiles<U>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        CU_LDS_BYTES));
+      raised[dev].store(true, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL(copy_kernel_tiles<U>, dim3((unsigned)std::min(tiles, cap)),
+                     dim3(BLOCK), lds, stream, (const uint4v*)src, (uint4v*)dst, n4);
+}
+
+// The one launch of the tile kernel, for copy(), copy_tiles and
+// copy_tiles_bw_gbps alike; the arguments have passed check_tiles_args.
+static void launch_copy_tiles(const void* src, void* dst, size_t n4, int unroll,
+                              int resident, int max_blocks, hipStream_t stream) {
+  switch (unroll) {
+    case 1: launch_copy_tiles_u<1>(src, dst, n4, resident, max_blocks, stream); break;
+    case 2: launch_copy_tiles_u<2>(src, dst, n4, resident, max_blocks, stream); break;
+    case 4: launch_copy_tiles_u<4>(src, dst, n4, resident, max_blocks, stream); break;
+    default: launch_copy_tiles_u<8>(src, dst, n4, resident, max_blocks, stream); break;
+  }
+}
+
 // read_sum_kernel sizes its LDS array for BLOCK threads.
 static void launch_read_sum(const void* src, size_t n4, void* out, int blocks,
                             hipStream_t stream) {
@@ -243,9 +352,8 @@ void copy(at::Tensor dst, at::Tensor src) {
   // 16 B vectors only for a whole number of them at aligned addresses;
   // a view at a 4-byte offset goes to the byte kernel like an odd size
   if ((((uintptr_t)src.data_ptr() | (uintptr_t)dst.data_ptr() | nbytes) & 15) == 0) {
-    size_t n4 = nbytes / 16;
-    int blocks = (int)std::min<size_t>((n4 + BLOCK - 1) / BLOCK, DEFAULT_COPY_BLOCKS);
-    launch_copy(src.data_ptr(), dst.data_ptr(), n4, 0, true, blocks, BLOCK, stream);
+    launch_copy_tiles(src.data_ptr(), dst.data_ptr(), nbytes / 16, COPY_TILES_UNROLL,
+                      COPY_TILES_RESIDENT, 0, stream);
   } else {
     int blocks = (int)std::min<size_t>((nbytes + BLOCK - 1) / BLOCK, 4096);
     hipLaunchKernelGGL(copy_kernel_b, dim3(blocks), dim3(BLOCK), 0, stream,
@@ -269,6 +377,21 @@ void copy_variant(at::Tensor dst, at::Tensor src, int64_t variant, bool nontempo
   auto stream = at::hip::getCurrentHIPStream();
   launch_copy(src.data_ptr(), dst.data_ptr(), n4, variant, nontemporal, blocks,
               threads, stream);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// One untimed launch of the tile kernel on the caller's tensors;
+// max_blocks > 0 caps the grid, so that workgroups loop over tiles.
+void copy_tiles(at::Tensor dst, at::Tensor src, int64_t unroll, int64_t resident,
+                int64_t max_blocks) {
+  check_pair(dst, src);
+  size_t n4 = check_vec_buf(src);
+  check_vec_buf(dst);
+  check_tiles_args(unroll, resident, max_blocks);
+  const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(dst));
+  auto stream = at::hip::getCurrentHIPStream();
+  launch_copy_tiles(src.data_ptr(), dst.data_ptr(), n4, (int)unroll, (int)resident,
+                    (int)max_blocks, stream);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -329,8 +452,27 @@ static float timed_ms(hipStream_t stream, int64_t iters, Launch&& launch) {
   return ms;
 }
 
-// Timed device-to-device streaming copy; returns achieved GB/s
-// (bytes read + bytes written over wall time, hipEvent-timed).
+// The body of the timed copy probes: a source of 0x01 bytes and a
+// poisoned destination, `launch(src, dst, stream)` timed, the destination
+// compared with the source; returns achieved GB/s (bytes read + bytes
+// written over wall time, hipEvent-timed).
+template <typename Launch>
+static double timed_copy_gbps(int64_t nbytes, int64_t iters, const std::string& who,
+                              Launch&& launch) {
+  auto opts = at::TensorOptions().dtype(at::kByte).device(at::kCUDA);
+  at::Tensor src = at::empty({nbytes}, opts);
+  at::Tensor dst = at::empty({nbytes}, opts);
+  src.fill_(1);
+  dst.fill_(POISON);
+  auto stream = at::hip::getCurrentHIPStream();
+  float ms = timed_ms(stream, iters,
+                      [&]() { launch(src.data_ptr(), dst.data_ptr(), stream); });
+  TORCH_CHECK(at::equal(dst, src), who, " produced wrong output");
+  double sec = ms / 1e3;
+  return (double)nbytes * 2.0 * iters / sec / 1e9;
+}
+
+// Timed device-to-device streaming copy with one of the variants 0..3.
 // blocks=0 picks the default; nontemporal selects the NT variant.
 double copy_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg,
                     bool nontemporal, int64_t variant, int64_t threads_arg) {
@@ -341,20 +483,22 @@ double copy_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg,
   // so the wave-granularity axis can be swept without new kernels
   int threads = check_threads(threads_arg);
   int blocks = pick_blocks(blocks_arg, n4, threads, DEFAULT_COPY_BLOCKS);
-  auto opts = at::TensorOptions().dtype(at::kByte).device(at::kCUDA);
-  at::Tensor src = at::empty({nbytes}, opts);
-  at::Tensor dst = at::empty({nbytes}, opts);
-  src.fill_(1);
-  dst.fill_(POISON);
-  auto stream = at::hip::getCurrentHIPStream();
-  float ms = timed_ms(stream, iters, [&]() {
-    launch_copy(src.data_ptr(), dst.data_ptr(), n4, variant, nontemporal, blocks,
-                threads, stream);
+  return timed_copy_gbps(nbytes, iters, "copy_bw_gbps: variant " + std::to_string(variant),
+                         [&](const void* src, void* dst, hipStream_t stream) {
+    launch_copy(src, dst, n4, variant, nontemporal, blocks, threads, stream);
   });
-  TORCH_CHECK(at::equal(dst, src), "copy_bw_gbps: variant ", variant,
-              " produced wrong output");
-  double sec = ms / 1e3;
-  return (double)nbytes * 2.0 * iters / sec / 1e9;
+}
+
+// The same measurement of the tile kernel (launch_copy_tiles).
+double copy_tiles_bw_gbps(int64_t nbytes, int64_t iters, int64_t unroll,
+                          int64_t resident, int64_t max_blocks) {
+  check_timed_args(nbytes, iters);
+  check_tiles_args(unroll, resident, max_blocks);
+  size_t n4 = (size_t)nbytes / 16;
+  return timed_copy_gbps(nbytes, iters, "copy_tiles_bw_gbps: the tile kernel",
+                         [&](const void* src, void* dst, hipStream_t stream) {
+    launch_copy_tiles(src, dst, n4, (int)unroll, (int)resident, (int)max_blocks, stream);
+  });
 }
 
 double write_bw_gbps(int64_t nbytes, int64_t iters, int64_t blocks_arg) {
@@ -433,6 +577,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dst"), py::arg("src"), py::arg("variant") = 0,
         py::arg("nontemporal") = true, py::arg("blocks") = 0,
         py::arg("threads") = 0);
+  m.def("copy_tiles", &copy_tiles,
+        "one untimed launch of the address-ordered tile copy kernel (dst, src)",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("dst"), py::arg("src"), py::arg("unroll"), py::arg("resident"),
+        py::arg("max_blocks") = 0);
+  m.def("copy_tiles_bw_gbps", &copy_tiles_bw_gbps,
+        "timed d2d copy bandwidth of the tile copy kernel",
+        py::call_guard<py::gil_scoped_release>(),
+        py::arg("nbytes"), py::arg("iters"), py::arg("unroll"), py::arg("resident"),
+        py::arg("max_blocks") = 0);
   m.def("read_sum", &read_sum, "u64 sum of all 32-bit words (one launch)",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("src"), py::arg("blocks") = 0);

@@ -5,6 +5,11 @@ The k=1 degenerate point of the BASELINE.md bandwidth curve: a 1-GPU
 streaming bandwidth from the hand-written CDNA4 copy kernel
 (csrc/gpuprobe.hip; ≈6.3 TB/s achievable of the 8 TB/s spec).
 
+copy() launches the address-ordered tile kernel with capped residency
+per CU; copy_tiles / d2d_copy_tiles_bw_gbps expose that kernel's tile
+size and cap, copy_variant / d2d_copy_bw_gbps the grid-stride kernels
+it is measured against.
+
 Fails LOUDLY when a GPU is present but the native extension is missing —
 GPU tests must never silently fall back to eager PyTorch.
 """
@@ -66,6 +71,19 @@ def copy_variant(
     load_ext().copy_variant(dst, src, variant, nontemporal, blocks, threads)
 
 
+def copy_tiles(dst, src, unroll: int, resident: int, max_blocks: int = 0) -> None:
+    """One untimed launch of the address-ordered tile copy kernel.
+
+    Tile t is the 256 * unroll consecutive 16-byte vectors from
+    t * 256 * unroll, one workgroup per tile; unroll is 1, 2, 4 or 8.
+    resident (1..8) keeps a CU from holding more than that many of the
+    workgroups at a time, 0 leaves it uncapped. max_blocks > 0 caps the
+    grid, so that workgroups loop over several tiles. Both tensors must
+    be 16-byte aligned with nbytes a multiple of 16.
+    """
+    load_ext().copy_tiles(dst, src, unroll, resident, max_blocks)
+
+
 def read_sum(src, blocks: int = 0) -> int:
     """Sum of all 32-bit words of src modulo 2**64 (one launch of the
     read_bw_gbps kernel into a zeroed accumulator)."""
@@ -91,6 +109,18 @@ def d2d_copy_bw_gbps(
     NT, 3 = regular loads + NT stores.
     """
     return load_ext().copy_bw_gbps(nbytes, iters, blocks, nontemporal, variant)
+
+
+def d2d_copy_tiles_bw_gbps(
+    nbytes: int = 1 << 30,
+    iters: int = 20,
+    unroll: int = 1,
+    resident: int = 0,
+    max_blocks: int = 0,
+) -> float:
+    """Timed bandwidth (GB/s, R+W) of the tile copy kernel: the same
+    launch as copy_tiles, timed and self-checked like d2d_copy_bw_gbps."""
+    return load_ext().copy_tiles_bw_gbps(nbytes, iters, unroll, resident, max_blocks)
 
 
 def read_bw_gbps(nbytes: int = 1 << 30, iters: int = 20, blocks: int = 0) -> float:
