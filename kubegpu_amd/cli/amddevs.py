@@ -30,6 +30,10 @@ Modes:
   amddevs --lanecheck     cross-lane (DPP, LDS crossbar, readlane, permlane
                           swaps) integrity probe over the idle GPUs, same
                           shape and exit codes ([--rounds N])
+  amddevs --ldscheck      LDS (narrow and wide accesses, bank conflicts,
+                          transposed read, LDS-DMA, cross-wave addressing)
+                          integrity probe over the idle GPUs, same shape and
+                          exit codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -43,7 +47,7 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import ALL_PROBES, EXIT_CANNOT_RUN
+from ..probe._active import EXIT_CANNOT_RUN, PROBES
 
 # probe -> (what the --fake backend lacks, size argument, name of its
 # default in the probe's module, result keys that count wrong data)
@@ -57,6 +61,7 @@ _PROBE_RUNS = {
     "atomcheck": ("atomic units", "rounds", "DEFAULT_ROUNDS",
                   ("mismatches", "shared_mismatches")),
     "lanecheck": ("cross-lane paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "ldscheck": ("LDS", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
 }
 
 
@@ -114,8 +119,8 @@ def main(argv=None) -> int:
                    help="run the compute-unit integrity probe on every GPU "
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
-                   help="with --cucheck, --mxcheck, --fpcheck, --atomcheck or --lanecheck: rounds "
-                        "per GPU "
+                   help="with --cucheck, --mxcheck, --fpcheck, --atomcheck, --lanecheck or "
+                        "--ldscheck: rounds per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
@@ -136,6 +141,11 @@ def main(argv=None) -> int:
                    help="run the cross-lane integrity probe (DPP, LDS "
                         "crossbar, readlane, permlane swaps) on every GPU this "
                         "command can see no allocation on")
+    p.add_argument("--ldscheck", action="store_true",
+                   help="run the LDS integrity probe (narrow and wide accesses, "
+                        "bank conflicts, transposed read, LDS-DMA, cross-wave "
+                        "addressing) on every GPU this command can see no "
+                        "allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -166,7 +176,7 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    for probe in ALL_PROBES:
+    for probe in PROBES:
         if getattr(args, probe):
             return _run_probe(probe, args, backend)
     if args.health:
@@ -187,6 +197,7 @@ def main(argv=None) -> int:
                 "fpcheck": mgr.fpcheck_status(uuid),
                 "atomcheck": mgr.atomcheck_status(uuid),
                 "lanecheck": mgr.lanecheck_status(uuid),
+                "ldscheck": mgr.ldscheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

@@ -554,6 +554,8 @@ void bind_fpcheck(py::module_& m);
 void bind_atomcheck(py::module_& m);
 // Cross-lane integrity kernel (lanecheck.hip, same extension).
 void bind_lanecheck(py::module_& m);
+// LDS integrity kernel (ldscheck.hip, same extension).
+void bind_ldscheck(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
@@ -564,6 +566,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_fpcheck(m);
   bind_atomcheck(m);
   bind_lanecheck(m);
+  bind_ldscheck(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
-from .probe._active import ALL_PROBES
+from .probe._active import PROBES
 
 try:
     from prometheus_client import (
@@ -110,6 +110,16 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "lanecheck runs that could not complete (not a cross-lane fault)"),
     ),
+    "ldscheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last LDS ldscheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last ldscheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed LDS ldscheck"),
+        ("err", "counter", "errors_total",
+         "ldscheck runs that could not complete (not an LDS fault)"),
+    ),
 }
 
 
@@ -123,7 +133,7 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         # gpu_<probe>: uuid -> what the last run's setter was given;
         # gpu_<probe>_errors: uuid -> runs that could not complete
-        for probe in ALL_PROBES:
+        for probe in PROBES:
             setattr(self, f"gpu_{probe}", {})
             setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
@@ -166,7 +176,7 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            for probe in ALL_PROBES:
+            for probe in PROBES:
                 for attr, kind, name, help_text in _PROBE_METRICS[probe]:
                     setattr(self, f"_{probe}_{attr}",
                             (Gauge if kind == "gauge" else Counter)(
@@ -294,6 +304,13 @@ class Metrics:
 
     def inc_lanecheck_error(self, uuid: str) -> None:
         self._inc_probe_error("lanecheck", uuid)
+
+    def set_gpu_ldscheck(self, uuid: str, mismatches: int, cus_covered: int,
+                         timestamp: float) -> None:
+        self._set_gpu_digests("ldscheck", uuid, mismatches, cus_covered, timestamp)
+
+    def inc_ldscheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("ldscheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

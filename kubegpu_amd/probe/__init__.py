@@ -107,6 +107,19 @@ _LANECHECK_EXPORTS = (
 )
 
 
+# LDS integrity probe (probe/ldscheck.py), the same way; the ldscheck()
+# function is `kubegpu_amd.probe.ldscheck.ldscheck`.  Its
+# reference_digests / wave_digests / wave_values stay in the submodule
+# too.
+_LDSCHECK_EXPORTS = (
+    "LdscheckResult",
+    "ldscheck_round",
+    "run_ldscheck_subprocess",
+    "source_tables",
+    "transposed_read",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
@@ -115,6 +128,7 @@ _LAZY_EXPORTS = {
     "hostlink": _HOSTLINK_EXPORTS,
     "atomcheck": _ATOMCHECK_EXPORTS,
     "lanecheck": _LANECHECK_EXPORTS,
+    "ldscheck": _LDSCHECK_EXPORTS,
 }
 
 

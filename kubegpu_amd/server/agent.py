@@ -25,7 +25,7 @@ from ..api import utils
 from ..deviceplugin import create_device_plugin
 from ..discovery import FakeBackend, default_backend, fixtures
 from ..metrics import METRICS
-from ..probe._active import ALL_PROBES
+from ..probe._active import PROBES
 from . import dpapi
 from .kubelet_plugin import KubeletDevicePlugin
 
@@ -144,6 +144,19 @@ def main(argv=None) -> int:
     ap.add_argument("--lanecheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the cross-lane integrity probe")
+    ap.add_argument("--ldscheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the LDS integrity probe (narrow and wide "
+                         "accesses, bank conflicts, transposed read, LDS-DMA, "
+                         "the whole array across waves) over the idle GPUs "
+                         "every SECONDS from the health loop; a GPU with a "
+                         "wrong digest turns Unhealthy (0 = off)")
+    ap.add_argument("--ldscheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the LDS integrity probe "
+                         "(default: the probe's own, about 0.5 s)")
+    ap.add_argument("--ldscheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the LDS integrity probe")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -198,7 +211,7 @@ def main(argv=None) -> int:
 
     watcher_started = False
     # first round of every enabled probe on the first tick
-    next_due = {probe: time.monotonic() for probe in ALL_PROBES}
+    next_due = {probe: time.monotonic() for probe in PROBES}
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -250,7 +263,7 @@ def main(argv=None) -> int:
         # after reconcile so in_use is current; a failed verdict flips
         # device_health(), so wake ListAndWatch again afterwards.  Their
         # children share one lock, so no two overlap on a GPU.
-        for probe in ALL_PROBES:
+        for probe in PROBES:
             interval = getattr(args, f"{probe}_interval")
             if not (interval > 0 and time.monotonic() >= next_due[probe]):
                 continue
