@@ -11,13 +11,15 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           (mxcheck), IEEE rounding integrity (fpcheck),
                           atomic-unit integrity (atomcheck),
                           cross-lane integrity (lanecheck), LDS
-                          integrity (ldscheck) and
+                          integrity (ldscheck), vector-memory
+                          integrity (vmemcheck) and
                           host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
                           csrc/pattern_common.h (patterns, mismatch
                           accounting, host-side argument checks and
                           pattern-family dispatch), cucheck, mxcheck,
-                          fpcheck, atomcheck, lanecheck and ldscheck
+                          fpcheck, atomcheck, lanecheck, ldscheck and
+                          vmemcheck
                           csrc/cucheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
@@ -100,13 +102,15 @@ def build_gpuprobe(verbose: bool = True) -> str:
     # integrity (cucheck) kernel + matrix-core format integrity (mxcheck)
     # kernel + IEEE rounding integrity (fpcheck) kernel + atomic-unit
     # integrity (atomcheck) kernel + cross-lane integrity (lanecheck)
-    # kernel + LDS integrity (ldscheck) kernel + host-link integrity
-    # (hostlink) kernels, one module;
+    # kernel + LDS integrity (ldscheck) kernel + vector-memory integrity
+    # (vmemcheck) kernel + host-link integrity (hostlink) kernels, one
+    # module;
     # fpcheck.hip relies on -O3 alone: no fast-math flag may be added here
     srcs = [os.path.join(CSRC, name)
             for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip",
                          "mxcheck.hip", "fpcheck.hip", "atomcheck.hip",
-                         "lanecheck.hip", "ldscheck.hip", "hostlink.hip")]
+                         "lanecheck.hip", "ldscheck.hip", "vmemcheck.hip",
+                         "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
     deps = srcs + [os.path.join(CSRC, name)
                    for name in ("pattern_common.h", "cucheck_common.h")]

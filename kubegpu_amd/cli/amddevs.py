@@ -34,6 +34,10 @@ Modes:
                           transposed read, LDS-DMA, cross-wave addressing)
                           integrity probe over the idle GPUs, same shape and
                           exit codes ([--rounds N])
+  amddevs --vmemcheck     vector-memory (narrow and wide global accesses,
+                          gathers through L1, scalar cache and L2, partial-line
+                          writes, buffer range check) integrity probe over the
+                          idle GPUs, same shape and exit codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -47,7 +51,7 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import EXIT_CANNOT_RUN, PROBES
+from ..probe._active import EXIT_CANNOT_RUN, PROBE_NAMES
 
 # probe -> (what the --fake backend lacks, size argument, name of its
 # default in the probe's module, result keys that count wrong data)
@@ -62,6 +66,7 @@ _PROBE_RUNS = {
                   ("mismatches", "shared_mismatches")),
     "lanecheck": ("cross-lane paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "ldscheck": ("LDS", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "vmemcheck": ("vector-memory paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
 }
 
 
@@ -119,8 +124,8 @@ def main(argv=None) -> int:
                    help="run the compute-unit integrity probe on every GPU "
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
-                   help="with --cucheck, --mxcheck, --fpcheck, --atomcheck, --lanecheck or "
-                        "--ldscheck: rounds per GPU "
+                   help="with --cucheck, --mxcheck, --fpcheck, --atomcheck, --lanecheck, "
+                        "--ldscheck or --vmemcheck: rounds per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
@@ -146,6 +151,11 @@ def main(argv=None) -> int:
                         "bank conflicts, transposed read, LDS-DMA, cross-wave "
                         "addressing) on every GPU this command can see no "
                         "allocation on")
+    p.add_argument("--vmemcheck", action="store_true",
+                   help="run the vector-memory integrity probe (narrow and wide "
+                        "global accesses, gathers through L1, scalar cache and "
+                        "L2, partial-line writes, buffer range check) on every "
+                        "GPU this command can see no allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -176,7 +186,7 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    for probe in PROBES:
+    for probe in PROBE_NAMES:
         if getattr(args, probe):
             return _run_probe(probe, args, backend)
     if args.health:
@@ -198,6 +208,7 @@ def main(argv=None) -> int:
                 "atomcheck": mgr.atomcheck_status(uuid),
                 "lanecheck": mgr.lanecheck_status(uuid),
                 "ldscheck": mgr.ldscheck_status(uuid),
+                "vmemcheck": mgr.vmemcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

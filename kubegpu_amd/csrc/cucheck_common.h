@@ -1,7 +1,7 @@
 // Hashing, digest folding, the kernels' argument block, the per-round
 // compare, mismatch accounting, argument checks, the timed launch and the
 // single-wave value launch shared by the integrity kernels that run one
-// 16-wave workgroup per compute unit; all six files compile into
+// 16-wave workgroup per compute unit; all seven files compile into
 // _gpuprobe and add only their stages, a fold / dump pair of sinks for
 // the stages' values and their own kernel arguments:
 //   cucheck.hip    i8 / bf16 matrix cores, VALU, LDS (lds_dwords)
@@ -10,6 +10,7 @@
 //   atomcheck.hip  LDS, L2 and memory-side atomics (arena, shared, drop)
 //   lanecheck.hip  the cross-lane data paths
 //   ldscheck.hip   the LDS array and its access paths (tables)
+//   vmemcheck.hip  the vector-memory and cache paths (arena, table)
 //
 // Every wave compares N_STAGES 32-bit digests per round with a table the
 // host computed in numpy.  Inputs are word(stage, r, idx) =

@@ -556,6 +556,8 @@ void bind_atomcheck(py::module_& m);
 void bind_lanecheck(py::module_& m);
 // LDS integrity kernel (ldscheck.hip, same extension).
 void bind_ldscheck(py::module_& m);
+// Vector-memory integrity kernel (vmemcheck.hip, same extension).
+void bind_vmemcheck(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
@@ -567,6 +569,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_atomcheck(m);
   bind_lanecheck(m);
   bind_ldscheck(m);
+  bind_vmemcheck(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

@@ -43,7 +43,7 @@ from ..discovery import (
     default_backend,
 )
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import PROBES
+from ..probe._active import PROBE_NAMES
 
 # Extracts the concrete GPU id out of a bound cards resource name
 # (cf. the reference's UUID regex at nvidia_gpu_manager.go:225).
@@ -90,7 +90,7 @@ class AMDGPUManager(Device):
         # the grace window expires: uuid -> (last GpuInfo, swept-at).
         self.vanished: Dict[str, tuple] = {}
         # Verdicts of the active probes, one dict per name in
-        # PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
+        # PROBE_NAMES: uuid -> verdict dict.  Kept here, not on GpuInfo,
         # because GpuInfo objects are replaced on every re-discovery and
         # the verdict must outlive them.
         # Active HBM integrity (memcheck) verdicts.
@@ -109,6 +109,8 @@ class AMDGPUManager(Device):
         self.lanecheck: Dict[str, dict] = {}
         # Active LDS integrity (ldscheck) verdicts, kept the same way.
         self.ldscheck: Dict[str, dict] = {}
+        # Active vector-memory integrity (vmemcheck) verdicts, kept the same way.
+        self.vmemcheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -200,7 +202,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
-                    for probe in PROBES:
+                    for probe in PROBE_NAMES:
                         getattr(self, probe).pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
@@ -214,7 +216,8 @@ class AMDGPUManager(Device):
 
         Present GPUs are healthy unless they report uncorrectable ECC
         errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
-        mxcheck, fpcheck, hostlink, atomcheck, lanecheck or ldscheck verdict;
+        mxcheck, fpcheck, hostlink, atomcheck, lanecheck, ldscheck or vmemcheck
+        verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -229,7 +232,7 @@ class AMDGPUManager(Device):
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
         """ECC health AND no failed verdict of any active probe (lock
         held)."""
-        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in PROBES)
+        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in PROBE_NAMES)
         return gpu.healthy and all(v is None or v["ok"] for v in verdicts)
 
     def _record(self, probe: str, uuid: str, result: dict, count_keys, describe) -> bool:
@@ -268,8 +271,8 @@ class AMDGPUManager(Device):
             return dict(v) if v is not None else None
 
     def _record_digests(self, probe: str, uuid: str, result: dict) -> bool:
-        """``_record`` for cucheck, mxcheck, fpcheck, lanecheck and ldscheck, whose results
-        (``DigestResult.to_dict()``) count ``mismatches``."""
+        """``_record`` for cucheck, mxcheck, fpcheck, lanecheck, ldscheck and
+        vmemcheck, whose results (``DigestResult.to_dict()``) count ``mismatches``."""
         return self._record(probe, uuid, result, ("mismatches",), lambda v: (
             probe + " FAILED on GPU %s: %d wrong digest(s), first bad round "
             "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
@@ -383,6 +386,15 @@ class AMDGPUManager(Device):
 
     def ldscheck_status(self, uuid: str) -> Optional[dict]:
         return self._status("ldscheck", uuid)
+
+    def record_vmemcheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("vmemcheck", uuid, result)
+
+    def clear_vmemcheck(self, uuid: str) -> bool:
+        return self._clear("vmemcheck", uuid)
+
+    def vmemcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("vmemcheck", uuid)
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:

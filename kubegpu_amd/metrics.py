@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
-from .probe._active import PROBES
+from .probe._active import PROBE_NAMES
 
 try:
     from prometheus_client import (
@@ -120,6 +120,16 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "ldscheck runs that could not complete (not an LDS fault)"),
     ),
+    "vmemcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last vector-memory vmemcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last vmemcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed vector-memory vmemcheck"),
+        ("err", "counter", "errors_total",
+         "vmemcheck runs that could not complete (not a memory-path fault)"),
+    ),
 }
 
 
@@ -133,7 +143,7 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         # gpu_<probe>: uuid -> what the last run's setter was given;
         # gpu_<probe>_errors: uuid -> runs that could not complete
-        for probe in PROBES:
+        for probe in PROBE_NAMES:
             setattr(self, f"gpu_{probe}", {})
             setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
@@ -176,7 +186,7 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            for probe in PROBES:
+            for probe in PROBE_NAMES:
                 for attr, kind, name, help_text in _PROBE_METRICS[probe]:
                     setattr(self, f"_{probe}_{attr}",
                             (Gauge if kind == "gauge" else Counter)(
@@ -311,6 +321,13 @@ class Metrics:
 
     def inc_ldscheck_error(self, uuid: str) -> None:
         self._inc_probe_error("ldscheck", uuid)
+
+    def set_gpu_vmemcheck(self, uuid: str, mismatches: int, cus_covered: int,
+                          timestamp: float) -> None:
+        self._set_gpu_digests("vmemcheck", uuid, mismatches, cus_covered, timestamp)
+
+    def inc_vmemcheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("vmemcheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

@@ -120,6 +120,18 @@ _LDSCHECK_EXPORTS = (
 )
 
 
+# Vector-memory integrity probe (probe/vmemcheck.py), the same way; the
+# vmemcheck() function is `kubegpu_amd.probe.vmemcheck.vmemcheck`.  Its
+# reference_digests / wave_digests / wave_values stay in the submodule
+# too.
+_VMEMCHECK_EXPORTS = (
+    "VmemcheckResult",
+    "vmemcheck_round",
+    "run_vmemcheck_subprocess",
+    "source_table",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
@@ -129,6 +141,7 @@ _LAZY_EXPORTS = {
     "atomcheck": _ATOMCHECK_EXPORTS,
     "lanecheck": _LANECHECK_EXPORTS,
     "ldscheck": _LDSCHECK_EXPORTS,
+    "vmemcheck": _VMEMCHECK_EXPORTS,
 }
 
 

@@ -1,5 +1,5 @@
 """What the active integrity probes (memcheck, cucheck, mxcheck,
-fpcheck, hostlink, atomcheck, lanecheck, ldscheck) share: the exit codes, the one child-process lock,
+fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck) share: the exit codes, the one child-process lock,
 the child runner, the round over a node's idle GPUs and the CLI body.
 Each probe module binds these to its own name, so a probe adds only
 what is its own: kernels, reference, result type.
@@ -25,9 +25,12 @@ HEALTH_PROBES: Tuple[str, ...] = ACTIVE_PROBES + ("atomcheck",)
 # The first seven probes whose verdict decides a GPU's health; later
 # probes are appended to PROBES below.
 ALL_PROBES: Tuple[str, ...] = HEALTH_PROBES + ("lanecheck",)
-# ALL_PROBES stays the first seven as well; this is the tuple those four
-# loops go through now.
+# ALL_PROBES stays the first seven as well, and PROBES the first eight.
 PROBES: Tuple[str, ...] = ALL_PROBES + ("ldscheck",)
+# Every probe whose verdict decides a GPU's health: the tuple the manager,
+# the metrics, the agent loop and the CLI go through; later probes are
+# appended here.
+PROBE_NAMES: Tuple[str, ...] = PROBES + ("vmemcheck",)
 
 EXIT_PASS, EXIT_MISMATCH, EXIT_CANNOT_RUN = 0, 1, 2
 

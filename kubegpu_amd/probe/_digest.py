@@ -1,5 +1,5 @@
 """What the digest probes (cucheck, mxcheck, fpcheck, atomcheck, lanecheck,
-ldscheck) share on the host: the hash that generates their inputs, the one-round and
+ldscheck, vmemcheck) share on the host: the hash that generates their inputs, the one-round and
 period helpers of their references, the result type, the run body, the
 decoding of the kernel's result block and of its value rows, and the dump
 run.  Their kernels share csrc/cucheck_common.h the same way.
@@ -184,7 +184,7 @@ def run_probe(name: str, res: DigestResult, stages: Sequence[str],
               work_per_wave_round: Sequence[int], unit: float, reference, seed: int,
               blocks: int, max_records: int, device, inject, expected, *extra) -> DigestResult:
     """The body of ``cucheck()``, ``mxcheck()``, ``fpcheck()``,
-    ``lanecheck()`` and ``ldscheck()``: ``res.rounds`` rounds of
+    ``lanecheck()``, ``ldscheck()`` and ``vmemcheck()``: ``res.rounds`` rounds of
     ``<name>_run`` against the table ``expected``, or ``reference()``
     where that is None, into ``res``.  ``extra`` goes between ``blocks``
     and ``max_records``."""
@@ -236,5 +236,5 @@ def wave_digests(name: str, run, table, stages: Sequence[str], seed: int, rounds
 
 def metric_args(rec: dict) -> tuple:
     """What ``set_gpu_cucheck`` / ``_mxcheck`` / ``_fpcheck`` / ``_lanecheck`` /
-    ``_ldscheck`` take of a result dict, before the timestamp."""
+    ``_ldscheck`` / ``_vmemcheck`` take of a result dict, before the timestamp."""
     return int(rec["mismatches"]), int(rec.get("cus_covered", 0))

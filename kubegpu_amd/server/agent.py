@@ -25,7 +25,7 @@ from ..api import utils
 from ..deviceplugin import create_device_plugin
 from ..discovery import FakeBackend, default_backend, fixtures
 from ..metrics import METRICS
-from ..probe._active import PROBES
+from ..probe._active import PROBE_NAMES
 from . import dpapi
 from .kubelet_plugin import KubeletDevicePlugin
 
@@ -157,6 +157,20 @@ def main(argv=None) -> int:
     ap.add_argument("--ldscheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the LDS integrity probe")
+    ap.add_argument("--vmemcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the vector-memory integrity probe (narrow and "
+                         "wide global accesses, gathers through the L1, the "
+                         "scalar cache and the L2, partial-line writes, the "
+                         "buffer range check) over the idle GPUs every SECONDS "
+                         "from the health loop; a GPU with a wrong digest "
+                         "turns Unhealthy (0 = off)")
+    ap.add_argument("--vmemcheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the vector-memory integrity probe "
+                         "(default: the probe's own, about 0.5 s)")
+    ap.add_argument("--vmemcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the vector-memory integrity probe")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -211,7 +225,7 @@ def main(argv=None) -> int:
 
     watcher_started = False
     # first round of every enabled probe on the first tick
-    next_due = {probe: time.monotonic() for probe in PROBES}
+    next_due = {probe: time.monotonic() for probe in PROBE_NAMES}
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -263,7 +277,7 @@ def main(argv=None) -> int:
         # after reconcile so in_use is current; a failed verdict flips
         # device_health(), so wake ListAndWatch again afterwards.  Their
         # children share one lock, so no two overlap on a GPU.
-        for probe in PROBES:
+        for probe in PROBE_NAMES:
             interval = getattr(args, f"{probe}_interval")
             if not (interval > 0 and time.monotonic() >= next_due[probe]):
                 continue
