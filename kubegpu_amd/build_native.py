@@ -12,14 +12,15 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           atomic-unit integrity (atomcheck),
                           cross-lane integrity (lanecheck), LDS
                           integrity (ldscheck), vector-memory
-                          integrity (vmemcheck) and
+                          integrity (vmemcheck), integer-ALU
+                          integrity (intcheck) and
                           host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
                           csrc/pattern_common.h (patterns, mismatch
                           accounting, host-side argument checks and
                           pattern-family dispatch), cucheck, mxcheck,
-                          fpcheck, atomcheck, lanecheck, ldscheck and
-                          vmemcheck
+                          fpcheck, atomcheck, lanecheck, ldscheck,
+                          vmemcheck and intcheck
                           csrc/cucheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
@@ -103,14 +104,14 @@ def build_gpuprobe(verbose: bool = True) -> str:
     # kernel + IEEE rounding integrity (fpcheck) kernel + atomic-unit
     # integrity (atomcheck) kernel + cross-lane integrity (lanecheck)
     # kernel + LDS integrity (ldscheck) kernel + vector-memory integrity
-    # (vmemcheck) kernel + host-link integrity (hostlink) kernels, one
-    # module;
+    # (vmemcheck) kernel + integer-ALU integrity (intcheck) kernel +
+    # host-link integrity (hostlink) kernels, one module;
     # fpcheck.hip relies on -O3 alone: no fast-math flag may be added here
     srcs = [os.path.join(CSRC, name)
             for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip",
                          "mxcheck.hip", "fpcheck.hip", "atomcheck.hip",
                          "lanecheck.hip", "ldscheck.hip", "vmemcheck.hip",
-                         "hostlink.hip")]
+                         "intcheck.hip", "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
     deps = srcs + [os.path.join(CSRC, name)
                    for name in ("pattern_common.h", "cucheck_common.h")]

@@ -38,6 +38,11 @@ Modes:
                           gathers through L1, scalar cache and L2, partial-line
                           writes, buffer range check) integrity probe over the
                           idle GPUs, same shape and exit codes ([--rounds N])
+  amddevs --intcheck      integer-ALU (shifts, bit fields, carry chains,
+                          multiplies and divisions, packed 16-bit math, integer
+                          dots, the scalar ALU, wave-mask arithmetic) integrity
+                          probe over the idle GPUs, same shape and exit codes
+                          ([--rounds N])
 """
 
 from __future__ import annotations
@@ -67,6 +72,7 @@ _PROBE_RUNS = {
     "lanecheck": ("cross-lane paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "ldscheck": ("LDS", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "vmemcheck": ("vector-memory paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "intcheck": ("integer ALUs", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
 }
 
 
@@ -125,7 +131,7 @@ def main(argv=None) -> int:
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
                    help="with --cucheck, --mxcheck, --fpcheck, --atomcheck, --lanecheck, "
-                        "--ldscheck or --vmemcheck: rounds per GPU "
+                        "--ldscheck, --vmemcheck or --intcheck: rounds per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
@@ -156,6 +162,12 @@ def main(argv=None) -> int:
                         "global accesses, gathers through L1, scalar cache and "
                         "L2, partial-line writes, buffer range check) on every "
                         "GPU this command can see no allocation on")
+    p.add_argument("--intcheck", action="store_true",
+                   help="run the integer-ALU integrity probe (shifts, bit fields, "
+                        "carry chains, multiplies and divisions, packed 16-bit "
+                        "math, integer dots, the scalar ALU, wave-mask "
+                        "arithmetic) on every GPU this command can see no "
+                        "allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -209,6 +221,7 @@ def main(argv=None) -> int:
                 "lanecheck": mgr.lanecheck_status(uuid),
                 "ldscheck": mgr.ldscheck_status(uuid),
                 "vmemcheck": mgr.vmemcheck_status(uuid),
+                "intcheck": mgr.intcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

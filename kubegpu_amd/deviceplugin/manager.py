@@ -111,6 +111,8 @@ class AMDGPUManager(Device):
         self.ldscheck: Dict[str, dict] = {}
         # Active vector-memory integrity (vmemcheck) verdicts, kept the same way.
         self.vmemcheck: Dict[str, dict] = {}
+        # Active integer-ALU integrity (intcheck) verdicts, kept the same way.
+        self.intcheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -216,8 +218,8 @@ class AMDGPUManager(Device):
 
         Present GPUs are healthy unless they report uncorrectable ECC
         errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
-        mxcheck, fpcheck, hostlink, atomcheck, lanecheck, ldscheck or vmemcheck
-        verdict;
+        mxcheck, fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck or
+        intcheck verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -271,8 +273,9 @@ class AMDGPUManager(Device):
             return dict(v) if v is not None else None
 
     def _record_digests(self, probe: str, uuid: str, result: dict) -> bool:
-        """``_record`` for cucheck, mxcheck, fpcheck, lanecheck, ldscheck and
-        vmemcheck, whose results (``DigestResult.to_dict()``) count ``mismatches``."""
+        """``_record`` for cucheck, mxcheck, fpcheck, lanecheck, ldscheck,
+        vmemcheck and intcheck, whose results (``DigestResult.to_dict()``) count
+        ``mismatches``."""
         return self._record(probe, uuid, result, ("mismatches",), lambda v: (
             probe + " FAILED on GPU %s: %d wrong digest(s), first bad round "
             "%s, stages %s, CUs (xcc/se/sh/cu) %s — marking Unhealthy",
@@ -395,6 +398,15 @@ class AMDGPUManager(Device):
 
     def vmemcheck_status(self, uuid: str) -> Optional[dict]:
         return self._status("vmemcheck", uuid)
+
+    def record_intcheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("intcheck", uuid, result)
+
+    def clear_intcheck(self, uuid: str) -> bool:
+        return self._clear("intcheck", uuid)
+
+    def intcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("intcheck", uuid)
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:

@@ -130,6 +130,16 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "vmemcheck runs that could not complete (not a memory-path fault)"),
     ),
+    "intcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last integer-ALU intcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last intcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed integer-ALU intcheck"),
+        ("err", "counter", "errors_total",
+         "intcheck runs that could not complete (not an ALU fault)"),
+    ),
 }
 
 
@@ -328,6 +338,13 @@ class Metrics:
 
     def inc_vmemcheck_error(self, uuid: str) -> None:
         self._inc_probe_error("vmemcheck", uuid)
+
+    def set_gpu_intcheck(self, uuid: str, mismatches: int, cus_covered: int,
+                         timestamp: float) -> None:
+        self._set_gpu_digests("intcheck", uuid, mismatches, cus_covered, timestamp)
+
+    def inc_intcheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("intcheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

@@ -132,6 +132,17 @@ _VMEMCHECK_EXPORTS = (
 )
 
 
+# Integer-ALU integrity probe (probe/intcheck.py), the same way; the
+# intcheck() function is `kubegpu_amd.probe.intcheck.intcheck`.  Its
+# reference_digests / wave_digests / wave_values stay in the submodule
+# too.
+_INTCHECK_EXPORTS = (
+    "IntcheckResult",
+    "intcheck_round",
+    "run_intcheck_subprocess",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
@@ -142,6 +153,7 @@ _LAZY_EXPORTS = {
     "lanecheck": _LANECHECK_EXPORTS,
     "ldscheck": _LDSCHECK_EXPORTS,
     "vmemcheck": _VMEMCHECK_EXPORTS,
+    "intcheck": _INTCHECK_EXPORTS,
 }
 
 

@@ -1,5 +1,5 @@
 """What the active integrity probes (memcheck, cucheck, mxcheck,
-fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck) share: the exit codes, the one child-process lock,
+fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck, intcheck) share: the exit codes, the one child-process lock,
 the child runner, the round over a node's idle GPUs and the CLI body.
 Each probe module binds these to its own name, so a probe adds only
 what is its own: kernels, reference, result type.
@@ -30,7 +30,7 @@ PROBES: Tuple[str, ...] = ALL_PROBES + ("ldscheck",)
 # Every probe whose verdict decides a GPU's health: the tuple the manager,
 # the metrics, the agent loop and the CLI go through; later probes are
 # appended here.
-PROBE_NAMES: Tuple[str, ...] = PROBES + ("vmemcheck",)
+PROBE_NAMES: Tuple[str, ...] = PROBES + ("vmemcheck", "intcheck")
 
 EXIT_PASS, EXIT_MISMATCH, EXIT_CANNOT_RUN = 0, 1, 2
 

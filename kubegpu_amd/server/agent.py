@@ -171,6 +171,20 @@ def main(argv=None) -> int:
     ap.add_argument("--vmemcheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the vector-memory integrity probe")
+    ap.add_argument("--intcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the integer-ALU integrity probe (shifts, bit "
+                         "fields, carry chains, multiplies and divisions, the "
+                         "packed 16-bit pipe, integer dots, the scalar ALU and "
+                         "the wave-mask arithmetic) over the idle GPUs every "
+                         "SECONDS from the health loop; a GPU with a wrong "
+                         "digest turns Unhealthy (0 = off)")
+    ap.add_argument("--intcheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the integer-ALU integrity probe "
+                         "(default: the probe's own, about 0.5 s)")
+    ap.add_argument("--intcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the integer-ALU integrity probe")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
