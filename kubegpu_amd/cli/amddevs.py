@@ -43,6 +43,11 @@ Modes:
                           dots, the scalar ALU, wave-mask arithmetic) integrity
                           probe over the idle GPUs, same shape and exit codes
                           ([--rounds N])
+  amddevs --transcheck    transcendental-unit (exp, log, rcp, rsq, sqrt, sin, cos
+                          in f32 and f16, the f64 approximations, v_prng_b32, and
+                          the sigmoid / GELU / RMS / log-sum-exp / rotary chains)
+                          integrity probe over the idle GPUs, same shape and exit
+                          codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -56,7 +61,7 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import EXIT_CANNOT_RUN, PROBE_NAMES
+from ..probe._active import EXIT_CANNOT_RUN, VERDICT_PROBES
 
 # probe -> (what the --fake backend lacks, size argument, name of its
 # default in the probe's module, result keys that count wrong data)
@@ -73,6 +78,7 @@ _PROBE_RUNS = {
     "ldscheck": ("LDS", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "vmemcheck": ("vector-memory paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "intcheck": ("integer ALUs", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "transcheck": ("transcendental units", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
 }
 
 
@@ -131,7 +137,7 @@ def main(argv=None) -> int:
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
                    help="with --cucheck, --mxcheck, --fpcheck, --atomcheck, --lanecheck, "
-                        "--ldscheck, --vmemcheck or --intcheck: rounds per GPU "
+                        "--ldscheck, --vmemcheck, --intcheck or --transcheck: rounds per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
@@ -168,6 +174,13 @@ def main(argv=None) -> int:
                         "math, integer dots, the scalar ALU, wave-mask "
                         "arithmetic) on every GPU this command can see no "
                         "allocation on")
+    p.add_argument("--transcheck", action="store_true",
+                   help="run the transcendental-unit integrity probe (exp, log, "
+                        "rcp, rsq, sqrt, sin, cos in f32 and f16, the f64 "
+                        "approximations, v_prng_b32 and dependent chains; one "
+                        "wave's values bounded by the host, then every wave "
+                        "bit-exact) on every GPU this command can see no "
+                        "allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -198,7 +211,7 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    for probe in PROBE_NAMES:
+    for probe in VERDICT_PROBES:
         if getattr(args, probe):
             return _run_probe(probe, args, backend)
     if args.health:
@@ -222,6 +235,7 @@ def main(argv=None) -> int:
                 "ldscheck": mgr.ldscheck_status(uuid),
                 "vmemcheck": mgr.vmemcheck_status(uuid),
                 "intcheck": mgr.intcheck_status(uuid),
+                "transcheck": mgr.transcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

@@ -560,6 +560,8 @@ void bind_ldscheck(py::module_& m);
 void bind_vmemcheck(py::module_& m);
 // Integer-ALU integrity kernel (intcheck.hip, same extension).
 void bind_intcheck(py::module_& m);
+// Transcendental-unit integrity kernel (transcheck.hip, same extension).
+void bind_transcheck(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
@@ -573,6 +575,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_ldscheck(m);
   bind_vmemcheck(m);
   bind_intcheck(m);
+  bind_transcheck(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
-from .probe._active import PROBE_NAMES
+from .probe._active import VERDICT_PROBES
 
 try:
     from prometheus_client import (
@@ -140,6 +140,17 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "intcheck runs that could not complete (not an ALU fault)"),
     ),
+    "transcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "golden-pass violations plus wave digests that came out wrong in the "
+         "last transcendental-unit transcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last transcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed transcendental-unit transcheck"),
+        ("err", "counter", "errors_total",
+         "transcheck runs that could not complete (not a transcendental-unit fault)"),
+    ),
 }
 
 
@@ -153,7 +164,7 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         # gpu_<probe>: uuid -> what the last run's setter was given;
         # gpu_<probe>_errors: uuid -> runs that could not complete
-        for probe in PROBE_NAMES:
+        for probe in VERDICT_PROBES:
             setattr(self, f"gpu_{probe}", {})
             setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
@@ -196,7 +207,7 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            for probe in PROBE_NAMES:
+            for probe in VERDICT_PROBES:
                 for attr, kind, name, help_text in _PROBE_METRICS[probe]:
                     setattr(self, f"_{probe}_{attr}",
                             (Gauge if kind == "gauge" else Counter)(
@@ -345,6 +356,13 @@ class Metrics:
 
     def inc_intcheck_error(self, uuid: str) -> None:
         self._inc_probe_error("intcheck", uuid)
+
+    def set_gpu_transcheck(self, uuid: str, mismatches: int, cus_covered: int,
+                           timestamp: float) -> None:
+        self._set_gpu_digests("transcheck", uuid, mismatches, cus_covered, timestamp)
+
+    def inc_transcheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("transcheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

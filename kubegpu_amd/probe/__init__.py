@@ -143,6 +143,17 @@ _INTCHECK_EXPORTS = (
 )
 
 
+# Transcendental-unit integrity probe (probe/transcheck.py), the same
+# way; the transcheck() function is
+# `kubegpu_amd.probe.transcheck.transcheck`.  Its golden / check_values /
+# fold_values / wave_values stay in the submodule too.
+_TRANSCHECK_EXPORTS = (
+    "TranscheckResult",
+    "transcheck_round",
+    "run_transcheck_subprocess",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
@@ -154,6 +165,7 @@ _LAZY_EXPORTS = {
     "ldscheck": _LDSCHECK_EXPORTS,
     "vmemcheck": _VMEMCHECK_EXPORTS,
     "intcheck": _INTCHECK_EXPORTS,
+    "transcheck": _TRANSCHECK_EXPORTS,
 }
 
 

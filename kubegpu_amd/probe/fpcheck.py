@@ -108,10 +108,11 @@ square root never, so recipe 2 builds none for them; f16 addends carry
 11 significant bits, so the sum of two cannot cancel by 20 binary
 orders unless it is zero (the f16 fma can: its product has 22 bits).
 
-Not covered: standalone v_exp, v_log, v_sin and v_cos — IEEE does not
-define their results, so no independent exact reference exists; their
-unit is reached only through the v_rcp, v_rsq and v_sqrt seeds inside
-division and square root.  fp8 conversions.  Rounding modes other than
+Not covered here: standalone v_exp, v_log, v_sin and v_cos — IEEE does
+not define their results, so no independent exact reference exists; this
+probe reaches their unit only through the v_rcp, v_rsq and v_sqrt seeds
+inside division and square root, and ``probe/transcheck.py`` covers it.
+fp8 conversions.  Rounding modes other than
 nearest-even.  Atomic operations, float ones included: they execute in
 units of their own, which are ``probe/atomcheck.py``'s ground.
 

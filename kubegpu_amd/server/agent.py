@@ -25,7 +25,7 @@ from ..api import utils
 from ..deviceplugin import create_device_plugin
 from ..discovery import FakeBackend, default_backend, fixtures
 from ..metrics import METRICS
-from ..probe._active import PROBE_NAMES
+from ..probe._active import VERDICT_PROBES
 from . import dpapi
 from .kubelet_plugin import KubeletDevicePlugin
 
@@ -185,6 +185,20 @@ def main(argv=None) -> int:
     ap.add_argument("--intcheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the integer-ALU integrity probe")
+    ap.add_argument("--transcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the transcendental-unit integrity probe (exp, "
+                         "log, rcp, rsq, sqrt, sin, cos in f32 and f16, the f64 "
+                         "approximations, v_prng_b32 and dependent chains) over "
+                         "the idle GPUs every SECONDS from the health loop; a "
+                         "GPU with a golden-pass violation or a wrong digest "
+                         "turns Unhealthy (0 = off)")
+    ap.add_argument("--transcheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the transcendental-unit integrity "
+                         "probe (default: the probe's own, about 0.5 s)")
+    ap.add_argument("--transcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the transcendental-unit integrity probe")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -239,7 +253,7 @@ def main(argv=None) -> int:
 
     watcher_started = False
     # first round of every enabled probe on the first tick
-    next_due = {probe: time.monotonic() for probe in PROBE_NAMES}
+    next_due = {probe: time.monotonic() for probe in VERDICT_PROBES}
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -291,7 +305,7 @@ def main(argv=None) -> int:
         # after reconcile so in_use is current; a failed verdict flips
         # device_health(), so wake ListAndWatch again afterwards.  Their
         # children share one lock, so no two overlap on a GPU.
-        for probe in PROBE_NAMES:
+        for probe in VERDICT_PROBES:
             interval = getattr(args, f"{probe}_interval")
             if not (interval > 0 and time.monotonic() >= next_due[probe]):
                 continue
