@@ -14,14 +14,15 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           integrity (ldscheck), vector-memory
                           integrity (vmemcheck), integer-ALU
                           integrity (intcheck), transcendental-unit
-                          integrity (transcheck) and
+                          integrity (transcheck), 16x16 / MX / sparse
+                          matrix-core integrity (matcheck) and
                           host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
                           csrc/pattern_common.h (patterns, mismatch
                           accounting, host-side argument checks and
                           pattern-family dispatch), cucheck, mxcheck,
                           fpcheck, atomcheck, lanecheck, ldscheck,
-                          vmemcheck, intcheck and transcheck
+                          vmemcheck, intcheck, transcheck and matcheck
                           csrc/cucheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
@@ -106,7 +107,8 @@ def build_gpuprobe(verbose: bool = True) -> str:
     # integrity (atomcheck) kernel + cross-lane integrity (lanecheck)
     # kernel + LDS integrity (ldscheck) kernel + vector-memory integrity
     # (vmemcheck) kernel + integer-ALU integrity (intcheck) kernel +
-    # transcendental-unit integrity (transcheck) kernel + host-link
+    # transcendental-unit integrity (transcheck) kernel + 16x16 / MX /
+    # sparse matrix-core integrity (matcheck) kernel + host-link
     # integrity (hostlink) kernels, one module;
     # fpcheck.hip and transcheck.hip rely on -O3 alone: no fast-math flag
     # may be added here
@@ -114,7 +116,8 @@ def build_gpuprobe(verbose: bool = True) -> str:
             for name in ("gpuprobe.hip", "memcheck.hip", "cucheck.hip",
                          "mxcheck.hip", "fpcheck.hip", "atomcheck.hip",
                          "lanecheck.hip", "ldscheck.hip", "vmemcheck.hip",
-                         "intcheck.hip", "transcheck.hip", "hostlink.hip")]
+                         "intcheck.hip", "transcheck.hip", "matcheck.hip",
+                         "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
     deps = srcs + [os.path.join(CSRC, name)
                    for name in ("pattern_common.h", "cucheck_common.h")]

@@ -48,6 +48,10 @@ Modes:
                           the sigmoid / GELU / RMS / log-sum-exp / rotary chains)
                           integrity probe over the idle GPUs, same shape and exit
                           codes ([--rounds N])
+  amddevs --matcheck      matrix-core (16x16 shapes, MXFP8 / MXFP6 / mixed formats
+                          with wide scales and op_sel, 2:4 structured sparsity)
+                          integrity probe over the idle GPUs, same shape and exit
+                          codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -61,7 +65,7 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import EXIT_CANNOT_RUN, VERDICT_PROBES
+from ..probe._active import EXIT_CANNOT_RUN, CHECK_PROBES
 
 # probe -> (what the --fake backend lacks, size argument, name of its
 # default in the probe's module, result keys that count wrong data)
@@ -79,6 +83,7 @@ _PROBE_RUNS = {
     "vmemcheck": ("vector-memory paths", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "intcheck": ("integer ALUs", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "transcheck": ("transcendental units", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "matcheck": ("matrix cores", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
 }
 
 
@@ -137,7 +142,7 @@ def main(argv=None) -> int:
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
                    help="with --cucheck, --mxcheck, --fpcheck, --atomcheck, --lanecheck, "
-                        "--ldscheck, --vmemcheck, --intcheck or --transcheck: rounds per GPU "
+                        "--ldscheck, --vmemcheck, --intcheck, --transcheck or --matcheck: rounds per GPU "
                         "(default: the probe's own, about 0.5 s)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
@@ -181,6 +186,13 @@ def main(argv=None) -> int:
                         "wave's values bounded by the host, then every wave "
                         "bit-exact) on every GPU this command can see no "
                         "allocation on")
+    p.add_argument("--matcheck", action="store_true",
+                   help="run the 16x16 / MXFP8 / MXFP6 / 2:4 sparse matrix-core "
+                        "integrity probe (dense 16x16 shapes, fp8 and fp6 elements "
+                        "of the scaled instruction with scales 23..230 in every "
+                        "byte of the scale register, Inf / NaN classes, the "
+                        "structured-sparse instructions and their index path) on "
+                        "every GPU this command can see no allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -211,7 +223,7 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    for probe in VERDICT_PROBES:
+    for probe in CHECK_PROBES:
         if getattr(args, probe):
             return _run_probe(probe, args, backend)
     if args.health:
@@ -236,6 +248,7 @@ def main(argv=None) -> int:
                 "vmemcheck": mgr.vmemcheck_status(uuid),
                 "intcheck": mgr.intcheck_status(uuid),
                 "transcheck": mgr.transcheck_status(uuid),
+                "matcheck": mgr.matcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

@@ -1,7 +1,7 @@
 // Hashing, digest folding, the kernels' argument block, the per-round
 // compare, mismatch accounting, argument checks, the timed launch and the
 // single-wave value launch shared by the integrity kernels that run one
-// 16-wave workgroup per compute unit; all nine files compile into
+// 16-wave workgroup per compute unit; all ten files compile into
 // _gpuprobe and add only their stages, a fold / dump pair of sinks for
 // the stages' values and their own kernel arguments:
 //   cucheck.hip    i8 / bf16 matrix cores, VALU, LDS (lds_dwords)
@@ -14,6 +14,7 @@
 //   intcheck.hip   the integer vector and scalar ALUs
 //   transcheck.hip the transcendental units (the table comes from one
 //                  wave of the GPU, bounded by the host)
+//   matcheck.hip   16x16 / MXFP8 / MXFP6 / 2:4 sparse matrix cores
 //
 // Every wave compares N_STAGES 32-bit digests per round with a table the
 // host computed in numpy.  Inputs are word(stage, r, idx) =

@@ -43,7 +43,7 @@ from ..discovery import (
     default_backend,
 )
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import VERDICT_PROBES
+from ..probe._active import CHECK_PROBES
 
 # Extracts the concrete GPU id out of a bound cards resource name
 # (cf. the reference's UUID regex at nvidia_gpu_manager.go:225).
@@ -90,7 +90,7 @@ class AMDGPUManager(Device):
         # the grace window expires: uuid -> (last GpuInfo, swept-at).
         self.vanished: Dict[str, tuple] = {}
         # Verdicts of the active probes, one dict per name in
-        # VERDICT_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
+        # CHECK_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
         # because GpuInfo objects are replaced on every re-discovery and
         # the verdict must outlive them.
         # Active HBM integrity (memcheck) verdicts.
@@ -115,6 +115,8 @@ class AMDGPUManager(Device):
         self.intcheck: Dict[str, dict] = {}
         # Active transcendental-unit integrity (transcheck) verdicts, kept the same way.
         self.transcheck: Dict[str, dict] = {}
+        # Active 16x16 / MX / sparse matrix-core integrity (matcheck) verdicts, kept the same way.
+        self.matcheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -206,7 +208,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
-                    for probe in VERDICT_PROBES:
+                    for probe in CHECK_PROBES:
                         getattr(self, probe).pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
@@ -221,7 +223,7 @@ class AMDGPUManager(Device):
         Present GPUs are healthy unless they report uncorrectable ECC
         errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
         mxcheck, fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck,
-        intcheck or transcheck verdict;
+        intcheck, transcheck or matcheck verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -236,7 +238,7 @@ class AMDGPUManager(Device):
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
         """ECC health AND no failed verdict of any active probe (lock
         held)."""
-        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in VERDICT_PROBES)
+        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in CHECK_PROBES)
         return gpu.healthy and all(v is None or v["ok"] for v in verdicts)
 
     def _record(self, probe: str, uuid: str, result: dict, count_keys, describe) -> bool:
@@ -276,7 +278,7 @@ class AMDGPUManager(Device):
 
     def _record_digests(self, probe: str, uuid: str, result: dict) -> bool:
         """``_record`` for cucheck, mxcheck, fpcheck, lanecheck, ldscheck,
-        vmemcheck, intcheck and transcheck, whose results
+        vmemcheck, intcheck, transcheck and matcheck, whose results
         (``DigestResult.to_dict()``) count ``mismatches`` (transcheck's hold its
         golden-pass violations too)."""
         return self._record(probe, uuid, result, ("mismatches",), lambda v: (
@@ -419,6 +421,15 @@ class AMDGPUManager(Device):
 
     def transcheck_status(self, uuid: str) -> Optional[dict]:
         return self._status("transcheck", uuid)
+
+    def record_matcheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("matcheck", uuid, result)
+
+    def clear_matcheck(self, uuid: str) -> bool:
+        return self._clear("matcheck", uuid)
+
+    def matcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("matcheck", uuid)
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:

@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
-from .probe._active import VERDICT_PROBES
+from .probe._active import CHECK_PROBES
 
 try:
     from prometheus_client import (
@@ -151,6 +151,17 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "transcheck runs that could not complete (not a transcendental-unit fault)"),
     ),
+    "matcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave digests that came out wrong in the last 16x16 / MX / sparse "
+         "matrix-core matcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last matcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed 16x16 / MX / sparse matrix-core matcheck"),
+        ("err", "counter", "errors_total",
+         "matcheck runs that could not complete (not a matrix-core fault)"),
+    ),
 }
 
 
@@ -164,7 +175,7 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         # gpu_<probe>: uuid -> what the last run's setter was given;
         # gpu_<probe>_errors: uuid -> runs that could not complete
-        for probe in VERDICT_PROBES:
+        for probe in CHECK_PROBES:
             setattr(self, f"gpu_{probe}", {})
             setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
@@ -207,7 +218,7 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            for probe in VERDICT_PROBES:
+            for probe in CHECK_PROBES:
                 for attr, kind, name, help_text in _PROBE_METRICS[probe]:
                     setattr(self, f"_{probe}_{attr}",
                             (Gauge if kind == "gauge" else Counter)(
@@ -363,6 +374,13 @@ class Metrics:
 
     def inc_transcheck_error(self, uuid: str) -> None:
         self._inc_probe_error("transcheck", uuid)
+
+    def set_gpu_matcheck(self, uuid: str, mismatches: int, cus_covered: int,
+                         timestamp: float) -> None:
+        self._set_gpu_digests("matcheck", uuid, mismatches, cus_covered, timestamp)
+
+    def inc_matcheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("matcheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

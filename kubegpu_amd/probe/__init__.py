@@ -154,6 +154,15 @@ _TRANSCHECK_EXPORTS = (
 )
 
 
+# 16x16 / MX / sparse matrix-core integrity probe (probe/matcheck.py), the
+# same way; the matcheck() function is `kubegpu_amd.probe.matcheck.matcheck`.
+_MATCHECK_EXPORTS = (
+    "MatcheckResult",
+    "matcheck_round",
+    "run_matcheck_subprocess",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
@@ -166,6 +175,7 @@ _LAZY_EXPORTS = {
     "vmemcheck": _VMEMCHECK_EXPORTS,
     "intcheck": _INTCHECK_EXPORTS,
     "transcheck": _TRANSCHECK_EXPORTS,
+    "matcheck": _MATCHECK_EXPORTS,
 }
 
 

@@ -1,6 +1,6 @@
 """What the active integrity probes (memcheck, cucheck, mxcheck,
 fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck, intcheck,
-transcheck) share: the exit codes, the one child-process lock,
+transcheck, matcheck) share: the exit codes, the one child-process lock,
 the child runner, the round over a node's idle GPUs and the CLI body.
 Each probe module binds these to its own name, so a probe adds only
 what is its own: kernels, reference, result type.
@@ -30,10 +30,12 @@ ALL_PROBES: Tuple[str, ...] = HEALTH_PROBES + ("lanecheck",)
 PROBES: Tuple[str, ...] = ALL_PROBES + ("ldscheck",)
 # PROBE_NAMES stays the first ten.
 PROBE_NAMES: Tuple[str, ...] = PROBES + ("vmemcheck", "intcheck")
+# VERDICT_PROBES stays the first eleven.
+VERDICT_PROBES: Tuple[str, ...] = PROBE_NAMES + ("transcheck",)
 # Every probe whose verdict decides a GPU's health: the tuple the manager,
 # the metrics, the agent loop and the CLI go through; later probes are
 # appended here.
-VERDICT_PROBES: Tuple[str, ...] = PROBE_NAMES + ("transcheck",)
+CHECK_PROBES: Tuple[str, ...] = VERDICT_PROBES + ("matcheck",)
 
 EXIT_PASS, EXIT_MISMATCH, EXIT_CANNOT_RUN = 0, 1, 2
 

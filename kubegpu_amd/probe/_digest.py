@@ -1,5 +1,5 @@
 """What the digest probes (cucheck, mxcheck, fpcheck, atomcheck, lanecheck,
-ldscheck, vmemcheck, intcheck, transcheck) share on the host: the hash that generates their inputs, the one-round and
+ldscheck, vmemcheck, intcheck, transcheck, matcheck) share on the host: the hash that generates their inputs, the one-round and
 period helpers of their references, the result type, the run body, the
 decoding of the kernel's result block and of its value rows, and the dump
 run.  Their kernels share csrc/cucheck_common.h the same way.
@@ -184,8 +184,8 @@ def run_probe(name: str, res: DigestResult, stages: Sequence[str],
               work_per_wave_round: Sequence[int], unit: float, reference, seed: int,
               blocks: int, max_records: int, device, inject, expected, *extra) -> DigestResult:
     """The body of ``cucheck()``, ``mxcheck()``, ``fpcheck()``,
-    ``lanecheck()``, ``ldscheck()``, ``vmemcheck()``, ``intcheck()`` and
-    ``transcheck()``:
+    ``lanecheck()``, ``ldscheck()``, ``vmemcheck()``, ``intcheck()``,
+    ``transcheck()`` and ``matcheck()``:
     ``res.rounds`` rounds of
     ``<name>_run`` against the table ``expected``, or ``reference()``
     where that is None, into ``res``.  ``extra`` goes between ``blocks``
@@ -238,6 +238,7 @@ def wave_digests(name: str, run, table, stages: Sequence[str], seed: int, rounds
 
 def metric_args(rec: dict) -> tuple:
     """What ``set_gpu_cucheck`` / ``_mxcheck`` / ``_fpcheck`` / ``_lanecheck`` /
-    ``_ldscheck`` / ``_vmemcheck`` / ``_intcheck`` / ``_transcheck`` take of a
+    ``_ldscheck`` / ``_vmemcheck`` / ``_intcheck`` / ``_transcheck`` /
+    ``_matcheck`` take of a
     result dict, before the timestamp."""
     return int(rec["mismatches"]), int(rec.get("cus_covered", 0))

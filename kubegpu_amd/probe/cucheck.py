@@ -40,7 +40,8 @@ exactly representable integer (bytes in bf16, sums below 2**24 in f32),
 so the reference is integer arithmetic — and rounding logic is therefore
 not covered: it is ``probe/fpcheck.py``'s ground.  The f16, fp8, MXFP4
 and f64 matrix paths are
-``probe/mxcheck.py``'s ground; the transcendental units are
+``probe/mxcheck.py``'s ground, the 16x16, MXFP8 / MXFP6 and sparse ones
+``probe/matcheck.py``'s; the transcendental units are
 ``probe/transcheck.py``'s, the path to HBM memcheck's.  The LDS stage uses plain
 reads and writes only: LDS, L2 and memory-side atomics are
 ``probe/atomcheck.py``'s ground.

@@ -57,6 +57,9 @@ Every stage uses only operands for which all partial sums are exactly
 representable in the accumulator type, so the reference is integer
 arithmetic, the result does not depend on the order the hardware sums
 in — and rounding logic is not covered (``probe/fpcheck.py``'s ground).
+The 16x16 shapes, the MXFP8 / MXFP6 formats with wide scales and op_sel,
+fp8 zero / subnormal / Inf / NaN and the 2:4 sparse instructions are
+``probe/matcheck.py``'s ground.
 
 How the kernel feeds the instructions (proved element by element by the
 GPU test of ``wave_tile`` against ``matmul_tile``): in the 32x32 stages

@@ -25,7 +25,7 @@ from ..api import utils
 from ..deviceplugin import create_device_plugin
 from ..discovery import FakeBackend, default_backend, fixtures
 from ..metrics import METRICS
-from ..probe._active import VERDICT_PROBES
+from ..probe._active import CHECK_PROBES
 from . import dpapi
 from .kubelet_plugin import KubeletDevicePlugin
 
@@ -199,6 +199,18 @@ def main(argv=None) -> int:
     ap.add_argument("--transcheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the transcendental-unit integrity probe")
+    ap.add_argument("--matcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the 16x16 / MXFP8 / MXFP6 / 2:4 sparse "
+                         "matrix-core integrity probe over the idle GPUs every "
+                         "SECONDS from the health loop; a GPU with a wrong "
+                         "digest turns Unhealthy (0 = off)")
+    ap.add_argument("--matcheck-rounds", type=int, default=None,
+                    help="rounds per GPU for the 16x16 / MX / sparse matrix-core "
+                         "integrity probe (default: the probe's own)")
+    ap.add_argument("--matcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the 16x16 / MX / sparse matrix-core integrity probe")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -253,7 +265,7 @@ def main(argv=None) -> int:
 
     watcher_started = False
     # first round of every enabled probe on the first tick
-    next_due = {probe: time.monotonic() for probe in VERDICT_PROBES}
+    next_due = {probe: time.monotonic() for probe in CHECK_PROBES}
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -305,7 +317,7 @@ def main(argv=None) -> int:
         # after reconcile so in_use is current; a failed verdict flips
         # device_health(), so wake ListAndWatch again afterwards.  Their
         # children share one lock, so no two overlap on a GPU.
-        for probe in VERDICT_PROBES:
+        for probe in CHECK_PROBES:
             interval = getattr(args, f"{probe}_interval")
             if not (interval > 0 and time.monotonic() >= next_due[probe]):
                 continue
