@@ -15,15 +15,16 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           integrity (vmemcheck), integer-ALU
                           integrity (intcheck), transcendental-unit
                           integrity (transcheck), 16x16 / MX / sparse
-                          matrix-core integrity (matcheck) and
-                          host-link integrity (hostlink) kernels;
+                          matrix-core integrity (matcheck), the
+                          tiled-GEMM load probe and NT GEMM (gemmcheck)
+                          and host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
                           csrc/pattern_common.h (patterns, mismatch
                           accounting, host-side argument checks and
                           pattern-family dispatch), cucheck, mxcheck,
                           fpcheck, atomcheck, lanecheck, ldscheck,
-                          vmemcheck, intcheck, transcheck and matcheck
-                          csrc/cucheck_common.h
+                          vmemcheck, intcheck, transcheck, matcheck and
+                          gemmcheck csrc/cucheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
 Rebuilds are skipped when the artifact is newer than its sources, the
@@ -108,8 +109,9 @@ def build_gpuprobe(verbose: bool = True) -> str:
     # kernel + LDS integrity (ldscheck) kernel + vector-memory integrity
     # (vmemcheck) kernel + integer-ALU integrity (intcheck) kernel +
     # transcendental-unit integrity (transcheck) kernel + 16x16 / MX /
-    # sparse matrix-core integrity (matcheck) kernel + host-link
-    # integrity (hostlink) kernels, one module;
+    # sparse matrix-core integrity (matcheck) kernel + tiled-GEMM load
+    # (gemmcheck) kernels + host-link integrity (hostlink) kernels, one
+    # module;
     # fpcheck.hip and transcheck.hip rely on -O3 alone: no fast-math flag
     # may be added here
     srcs = [os.path.join(CSRC, name)
@@ -117,7 +119,7 @@ def build_gpuprobe(verbose: bool = True) -> str:
                          "mxcheck.hip", "fpcheck.hip", "atomcheck.hip",
                          "lanecheck.hip", "ldscheck.hip", "vmemcheck.hip",
                          "intcheck.hip", "transcheck.hip", "matcheck.hip",
-                         "hostlink.hip")]
+                         "gemmcheck.hip", "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
     deps = srcs + [os.path.join(CSRC, name)
                    for name in ("pattern_common.h", "cucheck_common.h")]

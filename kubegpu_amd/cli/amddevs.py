@@ -52,6 +52,10 @@ Modes:
                           with wide scales and op_sel, 2:4 structured sparsity)
                           integrity probe over the idle GPUs, same shape and exit
                           codes ([--rounds N])
+  amddevs --gemmcheck     full-chip load probe (tiled bf16 and i8 GEMMs with HBM,
+                          L2, LDS and the matrix cores busy on every CU, folds
+                          compared bit for bit) over the idle GPUs, same shape and
+                          exit codes ([--rounds N])
 """
 
 from __future__ import annotations
@@ -65,7 +69,7 @@ from ..core import Cluster
 from ..deviceplugin import create_device_plugin
 from ..discovery import default_backend
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import EXIT_CANNOT_RUN, CHECK_PROBES
+from ..probe._active import EXIT_CANNOT_RUN, LOAD_PROBES
 
 # probe -> (what the --fake backend lacks, size argument, name of its
 # default in the probe's module, result keys that count wrong data)
@@ -84,6 +88,7 @@ _PROBE_RUNS = {
     "intcheck": ("integer ALUs", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "transcheck": ("transcendental units", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
     "matcheck": ("matrix cores", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
+    "gemmcheck": ("memory, LDS or matrix cores", "rounds", "DEFAULT_ROUNDS", ("mismatches",)),
 }
 
 
@@ -142,8 +147,9 @@ def main(argv=None) -> int:
                         "this command can see no allocation on")
     p.add_argument("--rounds", type=int, default=None, metavar="N",
                    help="with --cucheck, --mxcheck, --fpcheck, --atomcheck, --lanecheck, "
-                        "--ldscheck, --vmemcheck, --intcheck, --transcheck or --matcheck: rounds per GPU "
-                        "(default: the probe's own, about 0.5 s)")
+                        "--ldscheck, --vmemcheck, --intcheck, --transcheck, --matcheck or --gemmcheck: "
+                        "rounds per GPU (default: the probe's own, about 0.5 s; 1 s for "
+                        "--gemmcheck)")
     p.add_argument("--mxcheck", action="store_true",
                    help="run the matrix-core format integrity probe (f16, fp8, "
                         "MXFP4, f64) on every GPU this command can see no "
@@ -193,6 +199,12 @@ def main(argv=None) -> int:
                         "byte of the scale register, Inf / NaN classes, the "
                         "structured-sparse instructions and their index path) on "
                         "every GPU this command can see no allocation on")
+    p.add_argument("--gemmcheck", action="store_true",
+                   help="run the full-chip load probe (tiled bf16 and i8 GEMMs at "
+                        "8192 x 8192 x 8192 with HBM, L2, LDS and the matrix cores "
+                        "busy at once, every wave's fold of its part of C compared "
+                        "bit for bit) on every GPU this command can see no "
+                        "allocation on")
     p.add_argument("--health", action="store_true",
                    help="per-GPU health view (ECC totals, tombstones)")
     p.add_argument("--cdi", action="store_true",
@@ -223,7 +235,7 @@ def main(argv=None) -> int:
             return 1
         print(cdi_json(mgr._last_info))
         return 0
-    for probe in CHECK_PROBES:
+    for probe in LOAD_PROBES:
         if getattr(args, probe):
             return _run_probe(probe, args, backend)
     if args.health:
@@ -249,6 +261,7 @@ def main(argv=None) -> int:
                 "intcheck": mgr.intcheck_status(uuid),
                 "transcheck": mgr.transcheck_status(uuid),
                 "matcheck": mgr.matcheck_status(uuid),
+                "gemmcheck": mgr.gemmcheck_status(uuid),
             }
         print(json.dumps(rows, indent=1))
         return 0

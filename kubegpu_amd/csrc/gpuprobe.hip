@@ -565,6 +565,9 @@ void bind_transcheck(py::module_& m);
 // 16x16 / MXFP8 / MXFP6 / sparse matrix-core integrity kernel
 // (matcheck.hip, same extension).
 void bind_matcheck(py::module_& m);
+// Tiled-GEMM load probe and the public NT GEMM (gemmcheck.hip, same
+// extension).
+void bind_gemmcheck(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
@@ -580,6 +583,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_intcheck(m);
   bind_transcheck(m);
   bind_matcheck(m);
+  bind_gemmcheck(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

@@ -43,7 +43,7 @@ from ..discovery import (
     default_backend,
 )
 from ..plugintypes import RESOURCE_GPU
-from ..probe._active import CHECK_PROBES
+from ..probe._active import LOAD_PROBES
 
 # Extracts the concrete GPU id out of a bound cards resource name
 # (cf. the reference's UUID regex at nvidia_gpu_manager.go:225).
@@ -90,7 +90,7 @@ class AMDGPUManager(Device):
         # the grace window expires: uuid -> (last GpuInfo, swept-at).
         self.vanished: Dict[str, tuple] = {}
         # Verdicts of the active probes, one dict per name in
-        # CHECK_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
+        # LOAD_PROBES: uuid -> verdict dict.  Kept here, not on GpuInfo,
         # because GpuInfo objects are replaced on every re-discovery and
         # the verdict must outlive them.
         # Active HBM integrity (memcheck) verdicts.
@@ -117,6 +117,8 @@ class AMDGPUManager(Device):
         self.transcheck: Dict[str, dict] = {}
         # Active 16x16 / MX / sparse matrix-core integrity (matcheck) verdicts, kept the same way.
         self.matcheck: Dict[str, dict] = {}
+        # Active full-chip GEMM load (gemmcheck) verdicts, kept the same way.
+        self.gemmcheck: Dict[str, dict] = {}
 
     # -- Device interface --------------------------------------------------
 
@@ -208,7 +210,7 @@ class AMDGPUManager(Device):
                     del self.vanished[uuid]
                 elif now - self.vanished[uuid][1] > VANISHED_TTL_S:
                     del self.vanished[uuid]
-                    for probe in CHECK_PROBES:
+                    for probe in LOAD_PROBES:
                         getattr(self, probe).pop(uuid, None)
 
             self.path_to_id = {g.render_path: u for u, g in self.gpus.items() if g.render_path}
@@ -223,7 +225,7 @@ class AMDGPUManager(Device):
         Present GPUs are healthy unless they report uncorrectable ECC
         errors (GpuInfo.healthy) or carry a failed memcheck, cucheck,
         mxcheck, fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck,
-        intcheck, transcheck or matcheck verdict;
+        intcheck, transcheck, matcheck or gemmcheck verdict;
         tombstoned (recently-vanished) GPUs stay visible but always
         unhealthy so kubelet degrades allocatable instead of the node
         silently shrinking."""
@@ -238,7 +240,7 @@ class AMDGPUManager(Device):
     def _gpu_healthy(self, gpu: GpuInfo) -> bool:
         """ECC health AND no failed verdict of any active probe (lock
         held)."""
-        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in CHECK_PROBES)
+        verdicts = (getattr(self, probe).get(gpu.uuid) for probe in LOAD_PROBES)
         return gpu.healthy and all(v is None or v["ok"] for v in verdicts)
 
     def _record(self, probe: str, uuid: str, result: dict, count_keys, describe) -> bool:
@@ -278,7 +280,7 @@ class AMDGPUManager(Device):
 
     def _record_digests(self, probe: str, uuid: str, result: dict) -> bool:
         """``_record`` for cucheck, mxcheck, fpcheck, lanecheck, ldscheck,
-        vmemcheck, intcheck, transcheck and matcheck, whose results
+        vmemcheck, intcheck, transcheck, matcheck and gemmcheck, whose results
         (``DigestResult.to_dict()``) count ``mismatches`` (transcheck's hold its
         golden-pass violations too)."""
         return self._record(probe, uuid, result, ("mismatches",), lambda v: (
@@ -430,6 +432,15 @@ class AMDGPUManager(Device):
 
     def matcheck_status(self, uuid: str) -> Optional[dict]:
         return self._status("matcheck", uuid)
+
+    def record_gemmcheck(self, uuid: str, result: dict) -> bool:
+        return self._record_digests("gemmcheck", uuid, result)
+
+    def clear_gemmcheck(self, uuid: str) -> bool:
+        return self._clear("gemmcheck", uuid)
+
+    def gemmcheck_status(self, uuid: str) -> Optional[dict]:
+        return self._status("gemmcheck", uuid)
 
     def gpu_or_tombstone(self, uuid: str) -> Optional[GpuInfo]:
         with self._lock:

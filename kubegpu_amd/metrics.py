@@ -11,7 +11,7 @@ from __future__ import annotations
 import threading
 from typing import Dict, List, Optional
 
-from .probe._active import CHECK_PROBES
+from .probe._active import LOAD_PROBES
 
 try:
     from prometheus_client import (
@@ -162,6 +162,16 @@ _PROBE_METRICS = {
         ("err", "counter", "errors_total",
          "matcheck runs that could not complete (not a matrix-core fault)"),
     ),
+    "gemmcheck": (
+        ("mismatches", "gauge", "mismatches",
+         "wave folds that came out wrong in the last full-chip GEMM load gemmcheck"),
+        ("cus", "gauge", "cus_covered",
+         "distinct compute units that ran a wave of the last gemmcheck"),
+        ("ts", "gauge", "last_run_timestamp_seconds",
+         "unix time of the last completed full-chip GEMM load gemmcheck"),
+        ("err", "counter", "errors_total",
+         "gemmcheck runs that could not complete (not a hardware fault)"),
+    ),
 }
 
 
@@ -175,7 +185,7 @@ class Metrics:
         self.gpu_in_use: Dict[str, bool] = {}
         # gpu_<probe>: uuid -> what the last run's setter was given;
         # gpu_<probe>_errors: uuid -> runs that could not complete
-        for probe in CHECK_PROBES:
+        for probe in LOAD_PROBES:
             setattr(self, f"gpu_{probe}", {})
             setattr(self, f"gpu_{probe}_errors", {})
         if _HAVE_PROM:
@@ -218,7 +228,7 @@ class Metrics:
                 ["uuid"],
                 registry=self.registry,
             )
-            for probe in CHECK_PROBES:
+            for probe in LOAD_PROBES:
                 for attr, kind, name, help_text in _PROBE_METRICS[probe]:
                     setattr(self, f"_{probe}_{attr}",
                             (Gauge if kind == "gauge" else Counter)(
@@ -381,6 +391,13 @@ class Metrics:
 
     def inc_matcheck_error(self, uuid: str) -> None:
         self._inc_probe_error("matcheck", uuid)
+
+    def set_gpu_gemmcheck(self, uuid: str, mismatches: int, cus_covered: int,
+                          timestamp: float) -> None:
+        self._set_gpu_digests("gemmcheck", uuid, mismatches, cus_covered, timestamp)
+
+    def inc_gemmcheck_error(self, uuid: str) -> None:
+        self._inc_probe_error("gemmcheck", uuid)
 
     def percentile(self, q: float) -> Optional[float]:
         with self._lock:

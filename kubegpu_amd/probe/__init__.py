@@ -163,6 +163,17 @@ _MATCHECK_EXPORTS = (
 )
 
 
+# Full-chip GEMM load probe (probe/gemmcheck.py), the same way; the
+# gemmcheck() function is `kubegpu_amd.probe.gemmcheck.gemmcheck`.  gemm_nt
+# is the public NT GEMM of the same kernel.
+_GEMMCHECK_EXPORTS = (
+    "GemmcheckResult",
+    "gemm_nt",
+    "gemmcheck_round",
+    "run_gemmcheck_subprocess",
+)
+
+
 _LAZY_EXPORTS = {
     "memcheck": _MEMCHECK_EXPORTS,
     "cucheck": _CUCHECK_EXPORTS,
@@ -176,6 +187,7 @@ _LAZY_EXPORTS = {
     "intcheck": _INTCHECK_EXPORTS,
     "transcheck": _TRANSCHECK_EXPORTS,
     "matcheck": _MATCHECK_EXPORTS,
+    "gemmcheck": _GEMMCHECK_EXPORTS,
 }
 
 

@@ -1,6 +1,6 @@
 """What the active integrity probes (memcheck, cucheck, mxcheck,
 fpcheck, hostlink, atomcheck, lanecheck, ldscheck, vmemcheck, intcheck,
-transcheck, matcheck) share: the exit codes, the one child-process lock,
+transcheck, matcheck, gemmcheck) share: the exit codes, the one child-process lock,
 the child runner, the round over a node's idle GPUs and the CLI body.
 Each probe module binds these to its own name, so a probe adds only
 what is its own: kernels, reference, result type.
@@ -32,10 +32,12 @@ PROBES: Tuple[str, ...] = ALL_PROBES + ("ldscheck",)
 PROBE_NAMES: Tuple[str, ...] = PROBES + ("vmemcheck", "intcheck")
 # VERDICT_PROBES stays the first eleven.
 VERDICT_PROBES: Tuple[str, ...] = PROBE_NAMES + ("transcheck",)
-# Every probe whose verdict decides a GPU's health: the tuple the manager,
-# the metrics, the agent loop and the CLI go through; later probes are
-# appended here.
+# CHECK_PROBES stays the first twelve: the probes that isolate one unit.
 CHECK_PROBES: Tuple[str, ...] = VERDICT_PROBES + ("matcheck",)
+# Every probe whose verdict decides a GPU's health, the full-chip load
+# probe included: the tuple the manager, the metrics, the agent loop and
+# the CLI go through; later probes are appended here.
+LOAD_PROBES: Tuple[str, ...] = CHECK_PROBES + ("gemmcheck",)
 
 EXIT_PASS, EXIT_MISMATCH, EXIT_CANNOT_RUN = 0, 1, 2
 

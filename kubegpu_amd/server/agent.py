@@ -25,7 +25,7 @@ from ..api import utils
 from ..deviceplugin import create_device_plugin
 from ..discovery import FakeBackend, default_backend, fixtures
 from ..metrics import METRICS
-from ..probe._active import CHECK_PROBES
+from ..probe._active import LOAD_PROBES
 from . import dpapi
 from .kubelet_plugin import KubeletDevicePlugin
 
@@ -211,6 +211,17 @@ def main(argv=None) -> int:
     ap.add_argument("--matcheck-max-procs", type=int, default=0,
                     help="highest amdsmi process_count still treated as "
                          "idle by the 16x16 / MX / sparse matrix-core integrity probe")
+    ap.add_argument("--gemmcheck-interval", type=float, default=0.0,
+                    metavar="SECONDS",
+                    help="run the full-chip tiled-GEMM load probe over the idle "
+                         "GPUs every SECONDS from the health loop; a GPU with a "
+                         "wrong fold turns Unhealthy (0 = off)")
+    ap.add_argument("--gemmcheck-rounds", type=int, default=None,
+                    help="GEMMs per dtype and GPU for the full-chip load probe "
+                         "(default: the probe's own)")
+    ap.add_argument("--gemmcheck-max-procs", type=int, default=0,
+                    help="highest amdsmi process_count still treated as "
+                         "idle by the full-chip load probe")
     ap.add_argument("--oneshot", action="store_true",
                     help="start, print state, exit (plumbing check)")
     args = ap.parse_args(argv)
@@ -265,7 +276,7 @@ def main(argv=None) -> int:
 
     watcher_started = False
     # first round of every enabled probe on the first tick
-    next_due = {probe: time.monotonic() for probe in CHECK_PROBES}
+    next_due = {probe: time.monotonic() for probe in LOAD_PROBES}
     while not stop["flag"]:
         if not args.no_register and not registered:
             try:
@@ -317,7 +328,7 @@ def main(argv=None) -> int:
         # after reconcile so in_use is current; a failed verdict flips
         # device_health(), so wake ListAndWatch again afterwards.  Their
         # children share one lock, so no two overlap on a GPU.
-        for probe in CHECK_PROBES:
+        for probe in LOAD_PROBES:
             interval = getattr(args, f"{probe}_interval")
             if not (interval > 0 and time.monotonic() >= next_due[probe]):
                 continue
