@@ -16,7 +16,9 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           integrity (intcheck), transcendental-unit
                           integrity (transcheck), 16x16 / MX / sparse
                           matrix-core integrity (matcheck), the
-                          tiled-GEMM load probe and NT GEMM (gemmcheck)
+                          tiled-GEMM load probe and NT GEMM (gemmcheck,
+                          with its block-scaled MXFP8 / MXFP4 stages
+                          and MX GEMM in gemmcheck_mx)
                           and host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
                           csrc/pattern_common.h (patterns, mismatch
@@ -24,7 +26,8 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           pattern-family dispatch), cucheck, mxcheck,
                           fpcheck, atomcheck, lanecheck, ldscheck,
                           vmemcheck, intcheck, transcheck, matcheck and
-                          gemmcheck csrc/cucheck_common.h
+                          gemmcheck csrc/cucheck_common.h, the two
+                          gemmcheck files csrc/gemmcheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
 Rebuilds are skipped when the artifact is newer than its sources, the
@@ -110,7 +113,7 @@ def build_gpuprobe(verbose: bool = True) -> str:
     # (vmemcheck) kernel + integer-ALU integrity (intcheck) kernel +
     # transcendental-unit integrity (transcheck) kernel + 16x16 / MX /
     # sparse matrix-core integrity (matcheck) kernel + tiled-GEMM load
-    # (gemmcheck) kernels + host-link integrity (hostlink) kernels, one
+    # (gemmcheck, gemmcheck_mx) kernels + host-link integrity (hostlink) kernels, one
     # module;
     # fpcheck.hip and transcheck.hip rely on -O3 alone: no fast-math flag
     # may be added here
@@ -119,10 +122,11 @@ def build_gpuprobe(verbose: bool = True) -> str:
                          "mxcheck.hip", "fpcheck.hip", "atomcheck.hip",
                          "lanecheck.hip", "ldscheck.hip", "vmemcheck.hip",
                          "intcheck.hip", "transcheck.hip", "matcheck.hip",
-                         "gemmcheck.hip", "hostlink.hip")]
+                         "gemmcheck.hip", "gemmcheck_mx.hip", "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
     deps = srcs + [os.path.join(CSRC, name)
-                   for name in ("pattern_common.h", "cucheck_common.h")]
+                   for name in ("pattern_common.h", "cucheck_common.h",
+                                "gemmcheck_common.h")]
     suffix = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(EXT_DIR, "_gpuprobe" + suffix)
     alt = os.path.join(EXT_DIR, "_gpuprobe.so")

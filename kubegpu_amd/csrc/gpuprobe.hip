@@ -568,6 +568,9 @@ void bind_matcheck(py::module_& m);
 // Tiled-GEMM load probe and the public NT GEMM (gemmcheck.hip, same
 // extension).
 void bind_gemmcheck(py::module_& m);
+// Its block-scaled MXFP8 / MXFP4 stages and the public MX GEMM
+// (gemmcheck_mx.hip, same extension).
+void bind_gemmcheck_mx(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);
 
@@ -584,6 +587,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   bind_transcheck(m);
   bind_matcheck(m);
   bind_gemmcheck(m);
+  bind_gemmcheck_mx(m);
   bind_hostlink(m);
   // The timed probes release the GIL: a multi-second hipEvent-timed
   // block must not starve other Python threads (the node agent serves

@@ -165,10 +165,12 @@ _MATCHECK_EXPORTS = (
 
 # Full-chip GEMM load probe (probe/gemmcheck.py), the same way; the
 # gemmcheck() function is `kubegpu_amd.probe.gemmcheck.gemmcheck`.  gemm_nt
-# is the public NT GEMM of the same kernel.
+# is the public NT GEMM of the same kernel, gemm_mx_nt its block-scaled
+# MXFP8 / MXFP4 form.
 _GEMMCHECK_EXPORTS = (
     "GemmcheckResult",
     "gemm_nt",
+    "gemm_mx_nt",
     "gemmcheck_round",
     "run_gemmcheck_subprocess",
 )

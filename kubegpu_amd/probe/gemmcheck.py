@@ -6,11 +6,16 @@ in registers.  This one checks the GPU while it does the job it is
 scheduled for: ``C[M,N] = A[M,K] . Bt[N,K]^T`` with HBM, L2, LDS and the
 matrix cores busy on every CU at once, many GEMMs in one launch, in bf16
 (``v_mfma_f32_32x32x16_bf16``, f32 accumulators) and in i8
-(``v_mfma_i32_32x32x32_i8``, i32 accumulators).  Marginal parts fail under
-combined load first; ECC does not see a wrong product.  ``gemm_nt`` is the
-same kernel with a store sink: the public NT GEMM.
+(``v_mfma_i32_32x32x32_i8``, i32 accumulators) by default, and on request
+(``dtypes=``) in the block-scaled OCP MX formats mxfp8 (e4m3 elements) and
+mxfp4 (e2m1 elements, two per byte), both on
+``v_mfma_scale_f32_32x32x64_f8f6f4`` with one E8M0 scale byte per row and
+32 elements of K.  Marginal parts fail under combined load first; ECC does
+not see a wrong product.  ``gemm_nt`` and ``gemm_mx_nt`` are the same
+kernels with a store sink: the public NT GEMMs.
 
-The workload (csrc/gemmcheck.hip; this module is the definition).
+The workload (csrc/gemmcheck.hip, csrc/gemmcheck_mx.hip; this module is
+the definition).
 Arithmetic is mod 2**32; ``fmix32``, ``base``, ``salt`` are cucheck's:
 
   word(s, r, idx) = fmix32(base(seed, s, r) + idx)
@@ -32,6 +37,26 @@ is exact in f32; for i8 products are at most 2**14 and the sums stay below
 product of the two blocks (exact), folded per class and quadrant, and the
 GPU's folds are compared bit for bit: ``expected[class][quadrant]``.
 
+The MX stages (``MX_DTYPES``, stages 2 and 3 of the records), with
+``sext`` as above and the same fold over f32 bit patterns:
+
+  C[i][j]  = sum over k of A[i][k] 2**(SA[i][k // 32] - 127)
+                         * Bt[j][k] 2**(SB[j][k // 32] - 127)
+  mxfp8    A[i][k] = e4m3(sext(word(72, i % 256, k), 5)), Bt from word(73, ..):
+           the bf16 stage's integers -16..15, all exact in e4m3
+  mxfp4    A[i][k] = E2M1[word(72, i % 256, k) & 15], Bt from word(73, ..):
+           all sixteen codes; element 2b is the low nibble of byte b
+  SA[i][b] = 127 + ra(i % 256) + t(b),  SB[j][b] = 127 + cb(j % 256) - t(b)
+  ra(i) = sext(word(74, 0, i), 4), cb(j) = sext(word(75, 0, j), 4): -8..7
+  t(b)  = word(76, 0, b) % 17 - 8: -8..8
+
+matcheck's rule: every block of a dot product carries the product scale
+2**(ra + cb), so C[i][j] is an integer (mxfp4: a multiple of 1/4) times a
+power of two, every partial sum in any order is exact in f32 for K <= 32768
+(16 . 16 . K <= 2**23) and K <= 65536 (144 K < 2**24), and a wrong row's
+scale, a wrong block's scale or a wrong byte select changes the fold.  No
+NaN code and no 0xFF scale appears.
+
 A workgroup of four waves owns a tile and wave q its quadrant q; the
 kernel walks ``t = block; t < rounds * tiles; t += blocks`` with the round
 as the slow index, and ``step_tile`` is its map from ``t % tiles`` to
@@ -44,12 +69,20 @@ Measured on MI355X at 8192 x 8192 x 8192: 530 TFLOP/s in bf16 and 1252
 TOP/s in i8 sustained, 29 % of torch.matmul's bf16 rate on the same
 operands (DEFAULT_ROUNDS below, profiles/gemmcheck_mi355x.json).
 
+The MX stages, measured on MI355X at 8192 x 8192 x 8192 in windows of 2.0
+to 2.1 s alternating with the bf16 stage (profiles/gemmcheck_mx_mi355x.json):
+1229 TFLOP/s in mxfp8 (0.895 ms per round) and 2598 TFLOP/s in mxfp4
+(0.423 ms), with bf16 at 519 TFLOP/s (2.12 ms) in the same session.
+
 Not covered: power, clock and temperature under load; shapes that are no
-multiple of the tile; fp8 and MX operands; address tagging finer than the
-four classes (memcheck's and vmemcheck's ground).
+multiple of the tile; unscaled fp8, e5m2, fp6 and mixed-width operands
+under load (mxcheck and matcheck probe those instructions in isolation);
+NaN, Inf and scale-NaN under load; address tagging finer than the four
+classes (memcheck's and vmemcheck's ground).
 
 CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
     python -m kubegpu_amd.probe.gemmcheck --device INDEX [--rounds N] [--seed S]
+                                          [--dtypes bf16,i8,mxfp8,mxfp4]
 """
 
 from __future__ import annotations
@@ -62,11 +95,15 @@ from . import _active, _digest
 from ._digest import _base, _device, _fmix32, _salt
 
 DTYPES: Tuple[str, ...] = ("bf16", "i8")  # the kernel's stage 0 and 1
+MX_DTYPES: Tuple[str, ...] = ("mxfp8", "mxfp4")  # stage 2 and 3, on request only
+_STAGES = DTYPES + MX_DTYPES
 TILE = 128
 PERIOD = 256  # rows after which the operands' content repeats
-SLAB = {"bf16": 64, "i8": 128}  # elements of K per 128-byte slab
-MAX_K = {"bf16": 32768, "i8": 131071}
+SLAB = {"bf16": 64, "i8": 128, "mxfp8": 128, "mxfp4": 256}  # elements of K per 128-byte slab
+MAX_K = {"bf16": 32768, "i8": 131071, "mxfp8": 32768, "mxfp4": 65536}
+MX_BLOCK = 32  # elements of K per E8M0 scale
 _STAGE_A, _STAGE_BT = 70, 71
+_STAGE_MX_A, _STAGE_MX_BT, _STAGE_RA, _STAGE_CB, _STAGE_T = 72, 73, 74, 75, 76
 # One default run of both dtypes should hold the GPU for about a second.
 # Measured on MI355X at 8192 x 8192 x 8192 on the default grid (512
 # workgroups) in windows of 1.7 to 2.2 s (profiles/gemmcheck_mi355x.json):
@@ -79,10 +116,18 @@ DEFAULT_ROUNDS = 340
 
 # -- numpy definition ----------------------------------------------------------
 
-def _check_dtype(dtype: str) -> str:
-    if dtype not in DTYPES:
-        raise ValueError(f"gemmcheck: dtype must be one of {DTYPES}, got {dtype!r}")
+def _check_dtype(dtype: str, allowed: Tuple[str, ...] = DTYPES) -> str:
+    if dtype not in allowed:
+        raise ValueError(f"gemmcheck: dtype must be one of {allowed}, got {dtype!r}")
     return dtype
+
+
+def _check_k(dtype: str, k: int) -> int:
+    k = int(k)
+    if k < 1 or k % SLAB[dtype] or k > MAX_K[dtype]:
+        raise ValueError(f"gemmcheck: K must be a multiple of {SLAB[dtype]} in "
+                         f"{SLAB[dtype]}..{MAX_K[dtype]} for {dtype}, got {k}")
+    return k
 
 
 def operand_block(seed: int, dtype: str, k: int):
@@ -90,10 +135,7 @@ def operand_block(seed: int, dtype: str, k: int):
     import numpy as np
 
     _check_dtype(dtype)
-    seed, k = int(seed) & 0xFFFFFFFF, int(k)
-    if k < 1 or k % SLAB[dtype] or k > MAX_K[dtype]:
-        raise ValueError(f"gemmcheck: K must be a multiple of {SLAB[dtype]} in "
-                         f"{SLAB[dtype]}..{MAX_K[dtype]} for {dtype}, got {k}")
+    seed, k = int(seed) & 0xFFFFFFFF, _check_k(dtype, k)
     rows = np.arange(PERIOD, dtype=np.uint32)
     idx = np.arange(k, dtype=np.uint32)
     out = []
@@ -124,12 +166,90 @@ def operands(seed: int, dtype: str, m: int, n: int, k: int, device=None):
     return out[0], out[1]
 
 
+def e4m3_of_int(v):
+    """The e4m3 codes (uint8) of integers -16..16, all exactly representable."""
+    import numpy as np
+
+    mag = np.abs(np.asarray(v, dtype=np.int64))
+    e = np.floor(np.log2(np.maximum(mag, 1))).astype(np.int64)
+    code = ((e + 7) << 3) | ((mag << 3 >> e) & 7)  # mag >= 1 is normal in e4m3
+    return (np.where(mag == 0, 0, code) | np.where(np.asarray(v) < 0, 0x80, 0)).astype(np.uint8)
+
+
+def mx_operand_block(seed: int, dtype: str, k: int):
+    """The 256-row blocks the MX operands repeat, as uint8: (A codes [256, k],
+    SA [256, k // 32], Bt codes [256, k], SB [256, k // 32]); one element
+    code per entry, e4m3 bytes or e2m1 nibbles (``mx_pack`` packs them)."""
+    import numpy as np
+
+    _check_dtype(dtype, MX_DTYPES)
+    seed, k = int(seed) & 0xFFFFFFFF, _check_k(dtype, k)
+    rows = np.arange(PERIOD, dtype=np.uint32)
+    idx = np.arange(k, dtype=np.uint32)
+    blocks = np.arange(k // MX_BLOCK, dtype=np.uint32)
+    zero = np.zeros(1, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        codes = []
+        for stage in (_STAGE_MX_A, _STAGE_MX_BT):
+            w = _fmix32(_base(seed, stage, rows)[:, None] + idx[None, :])
+            if dtype == "mxfp8":
+                codes.append(e4m3_of_int(((w & np.uint32(31)) ^ np.uint32(16)).astype(np.int64) - 16))
+            else:
+                codes.append((w & np.uint32(15)).astype(np.uint8))
+        ra, cb = ((((_fmix32(_base(seed, stage, zero) + rows) & np.uint32(15)) ^ np.uint32(8))
+                   .astype(np.int64) - 8) for stage in (_STAGE_RA, _STAGE_CB))
+        t = (_fmix32(_base(seed, _STAGE_T, zero) + blocks) % np.uint32(17)).astype(np.int64) - 8
+    sa = (127 + ra[:, None] + t[None, :]).astype(np.uint8)
+    sb = (127 + cb[:, None] - t[None, :]).astype(np.uint8)
+    return codes[0], sa, codes[1], sb
+
+
+def mx_pack(dtype: str, codes):
+    """Element codes [rows, k] as the kernel reads them: e4m3 bytes as they
+    are, e2m1 nibbles two per byte with element 2b the low nibble of byte b."""
+    import numpy as np
+
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    if _check_dtype(dtype, MX_DTYPES) == "mxfp8":
+        return codes
+    return codes[:, 0::2] | (codes[:, 1::2] << 4)
+
+
+def mx_dequantise(dtype: str, codes, scales):
+    """The float64 values codes [rows, k] and E8M0 scales [rows, k // 32]
+    stand for (exact)."""
+    import numpy as np
+
+    from .mxcheck import E2M1, E4M3
+
+    table = np.array(E4M3 if _check_dtype(dtype, MX_DTYPES) == "mxfp8" else E2M1)
+    exp = np.repeat(np.asarray(scales).astype(np.int64), MX_BLOCK, axis=1) - 127
+    return np.ldexp(table[np.asarray(codes)], exp)
+
+
+def mx_operands(seed: int, dtype: str, m: int, n: int, k: int, device=None):
+    """(A, SA, Bt, SB) on the GPU as uint8, packed for ``gemm_mx_nt``: the
+    blocks of ``mx_operand_block`` uploaded once and repeated on the device."""
+    import torch
+
+    m, n = int(m), int(n)
+    if m < TILE or n < TILE or m % TILE or n % TILE:
+        raise ValueError(f"gemmcheck: M and N must be multiples of {TILE}, got {m} and {n}")
+    device = _device(device)
+    a, sa, bt, sb = mx_operand_block(seed, dtype, k)
+    out = []
+    for block, rows in ((mx_pack(dtype, a), m), (sa, m), (mx_pack(dtype, bt), n), (sb, n)):
+        t = torch.from_numpy(block).to(device)
+        out.append(t.repeat(-(-rows // PERIOD), 1)[:rows].contiguous())
+    return tuple(out)
+
+
 def tile_bits(dtype: str, c):
     """bits() of exact values c[...] as uint32."""
     import numpy as np
 
     c = np.asarray(c)
-    if _check_dtype(dtype) == "i8":
+    if _check_dtype(dtype, _STAGES) == "i8":
         return c.astype(np.int64).astype(np.uint32)
     b = c.astype(np.float32).view(np.uint32).copy()
     b[c == 0] = 0
@@ -162,7 +282,11 @@ def reference_expected(seed: int, dtype: str, k: int):
     GPU kernel is tested against."""
     import numpy as np
 
-    a, bt = operand_block(seed, dtype, k)
+    if dtype in MX_DTYPES:
+        a, sa, bt, sb = mx_operand_block(seed, dtype, k)
+        a, bt = mx_dequantise(dtype, a, sa), mx_dequantise(dtype, bt, sb)
+    else:
+        a, bt = operand_block(seed, dtype, k)
     c = a.astype(np.float64) @ bt.astype(np.float64).T  # exact: see the module docstring
     return fold_tiles(split_tiles(tile_bits(dtype, c))).reshape(4, 4)
 
@@ -213,7 +337,7 @@ class GemmcheckResult:
 
 
 def _decode(raw) -> dict:
-    rec = _digest.decode_record(raw, DTYPES)
+    rec = _digest.decode_record(raw, _STAGES)
     where = rec.pop("wave")
     del rec["block"]
     return dict(rec, tile=where >> 2, quadrant=where & 3, dtype=rec.pop("stage"))
@@ -234,7 +358,8 @@ def gemmcheck(
     """Run ``rounds`` GEMMs of [m, k] by [n, k] per dtype in one launch each
     on ``blocks`` workgroups of four waves (0 = two per CU, or one per tile
     step if that is fewer) and compare every wave's fold with
-    ``reference_expected``.
+    ``reference_expected``.  ``dtypes`` may name any of ``DTYPES`` and
+    ``MX_DTYPES``; the default is ``DTYPES``.
 
     The operands are taken from free VRAM: 2 (m + n) k bytes at most; where
     they do not fit the probe raises, which says nothing about the hardware.
@@ -258,16 +383,21 @@ def gemmcheck(
         raise RuntimeError(f"gemmcheck: operands need {need} bytes, {free} are free")
     with torch.cuda.device(device):
         for dtype in dtypes:
-            stage = DTYPES.index(_check_dtype(dtype))
-            a, bt = operands(seed, dtype, m, n, k, device)
+            stage = _STAGES.index(_check_dtype(dtype, _STAGES))
             table = reference_expected(seed, dtype, k)
             expected = _digest.expected_tensor("gemmcheck", table, 4, range(4), device)
             inject = None
             if _inject is not None and _inject[0] == dtype:
                 inject = (int(_inject[1]), int(_inject[2]), stage, int(_inject[3]))
-            count, first, _mask, records, waves_on, elapsed = ext.gemmcheck_run(
-                a, bt, expected, rounds, blocks, int(max_records), inject)
-            del a, bt
+            if dtype in MX_DTYPES:
+                ops = mx_operands(seed, dtype, m, n, k, device)
+                raw = ext.gemmcheck_mx_run(*ops, dtype, expected, rounds, blocks,
+                                           int(max_records), inject)
+            else:
+                ops = operands(seed, dtype, m, n, k, device)
+                raw = ext.gemmcheck_run(*ops, expected, rounds, blocks, int(max_records), inject)
+            del ops
+            count, first, _mask, records, waves_on, elapsed = raw
             res.waves_on = [x + int(y) for x, y in zip(res.waves_on, waves_on)]
             if count:
                 res.mismatches += int(count)
@@ -297,6 +427,22 @@ def gemm_nt(a, bt, blocks: int = 0):
         return _active._ext().gemm_nt(a, bt, int(blocks))
 
 
+def gemm_mx_nt(a, a_scale, bt, bt_scale, format: str, blocks: int = 0):
+    """The block-scaled NT GEMM on the GPU of the operands, float32 [M, N]:
+    ``sum_k a[i][k] 2**(a_scale[i][k // 32] - 127) bt[j][k] 2**(bt_scale[j][k // 32] - 127)``.
+    ``format`` "mxfp8": ``a [M, K]``, ``bt [N, K]`` hold e4m3 codes (uint8 or
+    float8_e4m3fn), K a multiple of 128, at most 32768.  "mxfp4": ``a [M, K / 2]``,
+    ``bt [N, K / 2]`` uint8 hold two e2m1 codes per byte, the low nibble
+    first, K a multiple of 256, at most 65536.  The scales are uint8 E8M0,
+    ``[M, K / 32]`` and ``[N, K / 32]``; M and N multiples of 128.  Exact
+    whenever every partial sum is representable in float32.  ``blocks``
+    workgroups walk the tiles (0 = two per CU)."""
+    import torch
+
+    with torch.cuda.device(a.device):
+        return _active._ext().gemm_mx_nt(a, a_scale, bt, bt_scale, str(format), int(blocks))
+
+
 # -- child process -----------------------------------------------------------
 
 def run_gemmcheck_subprocess(index: int, rounds: int = DEFAULT_ROUNDS,
@@ -314,9 +460,14 @@ def gemmcheck_round(manager, runner: Callable[[int, int], dict], metrics=None,
 
 
 def main(argv=None) -> int:
+    def add_arguments(ap):
+        ap.add_argument("--dtypes", default=",".join(DTYPES), metavar="NAMES",
+                        help="comma-separated stages to run, of " + ", ".join(_STAGES))
+
     return _active.probe_main(
         "gemmcheck", "--rounds", DEFAULT_ROUNDS,
-        lambda args: gemmcheck(seed=args.seed, rounds=args.rounds), argv)
+        lambda args: gemmcheck(seed=args.seed, rounds=args.rounds,
+                               dtypes=tuple(args.dtypes.split(","))), argv, add_arguments)
 
 
 if __name__ == "__main__":
