@@ -18,7 +18,8 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           matrix-core integrity (matcheck), the
                           tiled-GEMM load probe and NT GEMM (gemmcheck,
                           with its block-scaled MXFP8 / MXFP4 stages
-                          and MX GEMM in gemmcheck_mx)
+                          and MX GEMM in gemmcheck_mx, the e5m2, MXFP6
+                          and mixed-format ones in gemmcheck_mx6)
                           and host-link integrity (hostlink) kernels;
                           memcheck and hostlink share
                           csrc/pattern_common.h (patterns, mismatch
@@ -26,7 +27,7 @@ Artifacts (all inside the package so they ship with the repo snapshot):
                           pattern-family dispatch), cucheck, mxcheck,
                           fpcheck, atomcheck, lanecheck, ldscheck,
                           vmemcheck, intcheck, transcheck, matcheck and
-                          gemmcheck csrc/cucheck_common.h, the two
+                          gemmcheck csrc/cucheck_common.h, the three
                           gemmcheck files csrc/gemmcheck_common.h
                           (torch.utils.cpp_extension -> hipcc, gfx950)
 
@@ -113,7 +114,7 @@ def build_gpuprobe(verbose: bool = True) -> str:
     # (vmemcheck) kernel + integer-ALU integrity (intcheck) kernel +
     # transcendental-unit integrity (transcheck) kernel + 16x16 / MX /
     # sparse matrix-core integrity (matcheck) kernel + tiled-GEMM load
-    # (gemmcheck, gemmcheck_mx) kernels + host-link integrity (hostlink) kernels, one
+    # (gemmcheck, gemmcheck_mx, gemmcheck_mx6) kernels + host-link integrity (hostlink) kernels, one
     # module;
     # fpcheck.hip and transcheck.hip rely on -O3 alone: no fast-math flag
     # may be added here
@@ -122,7 +123,8 @@ def build_gpuprobe(verbose: bool = True) -> str:
                          "mxcheck.hip", "fpcheck.hip", "atomcheck.hip",
                          "lanecheck.hip", "ldscheck.hip", "vmemcheck.hip",
                          "intcheck.hip", "transcheck.hip", "matcheck.hip",
-                         "gemmcheck.hip", "gemmcheck_mx.hip", "hostlink.hip")]
+                         "gemmcheck.hip", "gemmcheck_mx.hip", "gemmcheck_mx6.hip",
+                         "hostlink.hip")]
     # included, not compiled: only the staleness check needs to see them
     deps = srcs + [os.path.join(CSRC, name)
                    for name in ("pattern_common.h", "cucheck_common.h",

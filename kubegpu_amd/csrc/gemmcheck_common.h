@@ -1,11 +1,13 @@
-// What gemmcheck.hip (bf16 / i8) and gemmcheck_mx.hip (MXFP8 / MXFP4)
-// share: the tile and LDS geometry, the kernels' arguments, the tile walk,
+// What gemmcheck.hip (bf16 / i8), gemmcheck_mx.hip (MXFP8 / MXFP4) and
+// gemmcheck_mx6.hip (e5m2, MXFP6 and mixed formats) share: the tile and LDS geometry, the kernels' arguments, the tile walk,
 // the two sinks for C, the default grid and the result block.  The header
 // comment of gemmcheck.hip explains each piece.
 
 #pragma once
 
 #include "cucheck_common.h"
+
+#include <string>
 
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
@@ -77,6 +79,19 @@ struct GcFold {
   }
 };
 
+// What the block-scaled kernels take: GcArgs and the scales, in the words
+// a slab's scale bytes of one row make: [128 tm, slabs] and [128 tn, slabs].
+struct GcmArgs {
+  GcArgs g;
+  const void* sa;
+  const void* sb;
+};
+
+__device__ __forceinline__ u32 gcm_f32_bits(float c) {
+  u32 b = __float_as_uint(c);
+  return (b << 1) == 0u ? 0u : b;
+}
+
 // ---------------------------------------------------------------- host
 
 // blocks = 0: two workgroups per CU, or one per step if that is fewer.
@@ -95,3 +110,24 @@ static inline at::Tensor gc_result_block(const at::Tensor& like, int64_t max_rec
   res.select(0, RES_FIRST).fill_(-1);  // u32 max: identity for atomicMin
   return res;
 }
+
+// The block-scaled files' host side.  A launcher starts one instantiation
+// of a kernel on `blocks` workgroups; gcm_gemm and gcm_run (gemmcheck_mx.hip)
+// are the bodies of gemm_mx_nt and gemmcheck_mx_run for any of them.
+typedef void (*GcmLaunch)(int64_t blocks, const CuArgs& ca, const GcmArgs& m);
+at::Tensor gcm_gemm(GcmArgs m, GcmLaunch store, const at::Tensor& a, int64_t blocks_arg);
+CucheckOut gcm_run(GcmArgs m, u32 stage, GcmLaunch fold, const at::Tensor& a,
+                   const at::Tensor& expected, int64_t rounds, int64_t blocks_arg,
+                   int64_t max_records, const c10::optional<CuInject>& inject);
+
+// A format of gemmcheck_mx6.hip: its stage of the records, its operand
+// checks (which fill the shape) and its two launchers.
+struct GcxFormat {
+  const char* name;
+  u32 stage;
+  GcmArgs (*check)(const at::Tensor& a, const at::Tensor& a_scale, const at::Tensor& bt,
+                   const at::Tensor& bt_scale);
+  GcmLaunch store, fold;
+};
+// null where `format` is none of that file's
+const GcxFormat* gcx_format(const std::string& format);

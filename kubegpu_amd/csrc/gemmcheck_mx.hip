@@ -109,22 +109,12 @@ struct GcmFp4 {
   static constexpr int64_t ELEMS_PER_BYTE = 2, MAX_K = GCM_MAX_K_FP4;
 };
 
-// GcArgs and the scales, in Scale words: [128 tm, slabs] and [128 tn, slabs].
-struct GcmArgs {
-  GcArgs g;
-  const void* sa;
-  const void* sb;
-};
+// GcmArgs (gemmcheck_common.h): the scales in Scale words.
 
 #define GCM_SCALE_ROWS 256u  // A and Bt rows of one stage
 template <typename T>
 constexpr size_t gcm_lds_bytes() {
   return GC_LDS_BYTES + 2 * GCM_SCALE_ROWS * sizeof(typename T::Scale);
-}
-
-__device__ __forceinline__ u32 gcm_f32_bits(float c) {
-  u32 b = __float_as_uint(c);
-  return (b << 1) == 0u ? 0u : b;
 }
 
 #if __HIP_DEVICE_COMPILE__
@@ -283,9 +273,11 @@ __global__ void __launch_bounds__(GC_THREADS, 2) gemmcheck_mx_kernel(CuArgs a, G
 
 // ---------------------------------------------------------------- host
 
+// The formats of gemmcheck_mx6.hip are looked up before this is asked.
 static bool gcm_is_fp4(const std::string& format) {
   TORCH_CHECK(format == "mxfp8" || format == "mxfp4",
-              "gemmcheck: format must be 'mxfp8' or 'mxfp4', got '", format, "'");
+              "gemmcheck: format must be 'mxfp8', 'mxfp4', 'mxfp8_e5m2', 'mxfp6_e2m3', "
+              "'mxfp6_e3m2' or 'mxfp8_e5m2:mxfp8', got '", format, "'");
   return format == "mxfp4";
 }
 
@@ -353,10 +345,7 @@ static void gcm_launch(int64_t blocks, const CuArgs& ca, const GcmArgs& m) {
                      at::hip::getCurrentHIPStream(), ca, m);
 }
 
-template <typename T>
-static at::Tensor gcm_gemm(const at::Tensor& a, const at::Tensor& a_scale, const at::Tensor& bt,
-                           const at::Tensor& bt_scale, int64_t blocks_arg) {
-  GcmArgs m = gcm_check_operands<T>(a, a_scale, bt, bt_scale);
+at::Tensor gcm_gemm(GcmArgs m, GcmLaunch store, const at::Tensor& a, int64_t blocks_arg) {
   const at::hip::OptionalHIPGuardMasqueradingAsCUDA guard(at::device_of(a));
   const int64_t blocks = gc_grid(blocks_arg, m.g.steps);
   at::Tensor out = at::empty({(int64_t)m.g.tm * GC_TILE, (int64_t)m.g.tn * GC_TILE},
@@ -364,7 +353,7 @@ static at::Tensor gcm_gemm(const at::Tensor& a, const at::Tensor& a_scale, const
   at::Tensor res = gc_result_block(out, 0);  // only the per-CU wave table is used
   m.g.out = (u32*)out.data_ptr();
   const CuArgs ca = {0, 1, nullptr, (u32*)res.data_ptr(), 0, nullptr, NO_INJECT, 0, 0, 0};
-  gcm_launch<T, GcStore>(blocks, ca, m);
+  store(blocks, ca, m);
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
@@ -373,16 +362,18 @@ static at::Tensor gcm_gemm(const at::Tensor& a, const at::Tensor& a_scale, const
 // operands.  Exact whenever every partial sum is representable in f32.
 at::Tensor gemm_mx_nt(at::Tensor a, at::Tensor a_scale, at::Tensor bt, at::Tensor bt_scale,
                       std::string format, int64_t blocks_arg) {
-  return gcm_is_fp4(format) ? gcm_gemm<GcmFp4>(a, a_scale, bt, bt_scale, blocks_arg)
-                            : gcm_gemm<GcmFp8>(a, a_scale, bt, bt_scale, blocks_arg);
+  if (const GcxFormat* x = gcx_format(format))
+    return gcm_gemm(x->check(a, a_scale, bt, bt_scale), x->store, a, blocks_arg);
+  return gcm_is_fp4(format)
+             ? gcm_gemm(gcm_check_operands<GcmFp4>(a, a_scale, bt, bt_scale),
+                        gcm_launch<GcmFp4, GcStore>, a, blocks_arg)
+             : gcm_gemm(gcm_check_operands<GcmFp8>(a, a_scale, bt, bt_scale),
+                        gcm_launch<GcmFp8, GcStore>, a, blocks_arg);
 }
 
-template <typename T>
-static CucheckOut gcm_run(const at::Tensor& a, const at::Tensor& a_scale, const at::Tensor& bt,
-                          const at::Tensor& bt_scale, const at::Tensor& expected, int64_t rounds,
-                          int64_t blocks_arg, int64_t max_records,
-                          const c10::optional<CuInject>& inject) {
-  GcmArgs m = gcm_check_operands<T>(a, a_scale, bt, bt_scale);
+CucheckOut gcm_run(GcmArgs m, u32 stage, GcmLaunch fold, const at::Tensor& a,
+                   const at::Tensor& expected, int64_t rounds, int64_t blocks_arg,
+                   int64_t max_records, const c10::optional<CuInject>& inject) {
   TORCH_CHECK(rounds >= 1 && rounds <= MAX_ROUNDS, "gemmcheck: rounds must be in 1..",
               MAX_ROUNDS, ", got ", rounds);
   TORCH_CHECK(rounds * (int64_t)m.g.steps <= GC_MAX_STEPS,
@@ -402,7 +393,7 @@ static CucheckOut gcm_run(const at::Tensor& a, const at::Tensor& a_scale, const 
   if (inject.has_value()) {
     int64_t w = std::get<0>(*inject), r = std::get<1>(*inject);
     int64_t s = std::get<2>(*inject), mask = std::get<3>(*inject);
-    TORCH_CHECK(w >= 0 && w < blocks * GC_WAVES && r >= 0 && r < rounds && s == T::STAGE &&
+    TORCH_CHECK(w >= 0 && w < blocks * GC_WAVES && r >= 0 && r < rounds && s == (int64_t)stage &&
                     mask >= 0 && mask <= 0xFFFFFFFFLL,
                 "gemmcheck: inject (wave, round, stage, mask) out of range");
     ca.inj_wave = (u32)w;
@@ -416,7 +407,7 @@ static CucheckOut gcm_run(const at::Tensor& a, const at::Tensor& a_scale, const 
   C10_HIP_CHECK(hipEventCreate(&t0));
   C10_HIP_CHECK(hipEventCreate(&t1));
   C10_HIP_CHECK(hipEventRecord(t0, stream));
-  gcm_launch<T, GcFold>(blocks, ca, m);
+  fold(blocks, ca, m);
   hipError_t launch_err = hipGetLastError();
   (void)hipEventRecord(t1, stream);
   hipError_t sync_err = hipEventSynchronize(t1);
@@ -431,23 +422,30 @@ static CucheckOut gcm_run(const at::Tensor& a, const at::Tensor& a_scale, const 
 
 // gemmcheck_run for the MX stages: `rounds` GEMMs in one launch, every
 // wave's fold compared with expected[class][quadrant]; nothing of C is
-// stored.  inject = (wave of the grid, round, stage 2 or 3, mask).
+// stored.  inject = (wave of the grid, round, the format's stage 2..7, mask).
 CucheckOut gemmcheck_mx_run(at::Tensor a, at::Tensor a_scale, at::Tensor bt, at::Tensor bt_scale,
                             std::string format, at::Tensor expected, int64_t rounds,
                             int64_t blocks_arg, int64_t max_records,
                             c10::optional<CuInject> inject) {
+  if (const GcxFormat* x = gcx_format(format))
+    return gcm_run(x->check(a, a_scale, bt, bt_scale), x->stage, x->fold, a, expected, rounds,
+                   blocks_arg, max_records, inject);
   return gcm_is_fp4(format)
-             ? gcm_run<GcmFp4>(a, a_scale, bt, bt_scale, expected, rounds, blocks_arg,
-                               max_records, inject)
-             : gcm_run<GcmFp8>(a, a_scale, bt, bt_scale, expected, rounds, blocks_arg,
-                               max_records, inject);
+             ? gcm_run(gcm_check_operands<GcmFp4>(a, a_scale, bt, bt_scale), GcmFp4::STAGE,
+                       gcm_launch<GcmFp4, GcFold>, a, expected, rounds, blocks_arg, max_records,
+                       inject)
+             : gcm_run(gcm_check_operands<GcmFp8>(a, a_scale, bt, bt_scale), GcmFp8::STAGE,
+                       gcm_launch<GcmFp8, GcFold>, a, expected, rounds, blocks_arg, max_records,
+                       inject);
 }
 
 // Called from gpuprobe.hip's PYBIND11_MODULE, GIL released like gemmcheck's.
 void bind_gemmcheck_mx(py::module_& m) {
   m.def("gemm_mx_nt", &gemm_mx_nt,
-        "C (float32) = a 2^(a_scale - 127) . (bt 2^(bt_scale - 127))^T, format 'mxfp8' (e4m3) "
-        "or 'mxfp4' (packed e2m1), one E8M0 scale per row and 32 elements of K",
+        "C (float32) = a 2^(a_scale - 127) . (bt 2^(bt_scale - 127))^T, format 'mxfp8' (e4m3), "
+        "'mxfp4' (packed e2m1), 'mxfp8_e5m2', 'mxfp6_e2m3', 'mxfp6_e3m2' (packed, 24 bytes per "
+        "32 elements) or 'mxfp8_e5m2:mxfp8' (a's format : bt's), one E8M0 scale per "
+        "row and 32 elements of K",
         py::call_guard<py::gil_scoped_release>(),
         py::arg("a"), py::arg("a_scale"), py::arg("bt"), py::arg("bt_scale"), py::arg("format"),
         py::arg("blocks") = 0);

@@ -569,7 +569,8 @@ void bind_matcheck(py::module_& m);
 // extension).
 void bind_gemmcheck(py::module_& m);
 // Its block-scaled MXFP8 / MXFP4 stages and the public MX GEMM
-// (gemmcheck_mx.hip, same extension).
+// (gemmcheck_mx.hip and, for e5m2, MXFP6 and e5m2 x e4m3, gemmcheck_mx6.hip,
+// same extension).
 void bind_gemmcheck_mx(py::module_& m);
 // Host-link integrity kernels (hostlink.hip, same extension).
 void bind_hostlink(py::module_& m);

@@ -8,14 +8,14 @@ matrix cores busy on every CU at once, many GEMMs in one launch, in bf16
 (``v_mfma_f32_32x32x16_bf16``, f32 accumulators) and in i8
 (``v_mfma_i32_32x32x32_i8``, i32 accumulators) by default, and on request
 (``dtypes=``) in the block-scaled OCP MX formats mxfp8 (e4m3 elements) and
-mxfp4 (e2m1 elements, two per byte), both on
-``v_mfma_scale_f32_32x32x64_f8f6f4`` with one E8M0 scale byte per row and
-32 elements of K.  Marginal parts fail under combined load first; ECC does
-not see a wrong product.  ``gemm_nt`` and ``gemm_mx_nt`` are the same
-kernels with a store sink: the public NT GEMMs.
+mxfp4 (e2m1 elements, two per byte), and in the rest of the family
+(``MX_EXT_DTYPES``: e5m2, the two packed fp6 formats and e5m2 x e4m3), all on ``v_mfma_scale_f32_32x32x64_f8f6f4`` with one E8M0 scale
+byte per row and 32 elements of K.  Marginal parts fail under combined load
+first; ECC does not see a wrong product.  ``gemm_nt`` and ``gemm_mx_nt``
+are the same kernels with a store sink: the public NT GEMMs.
 
-The workload (csrc/gemmcheck.hip, csrc/gemmcheck_mx.hip; this module is
-the definition).
+The workload (csrc/gemmcheck.hip, csrc/gemmcheck_mx.hip,
+csrc/gemmcheck_mx6.hip; this module is the definition).
 Arithmetic is mod 2**32; ``fmix32``, ``base``, ``salt`` are cucheck's:
 
   word(s, r, idx) = fmix32(base(seed, s, r) + idx)
@@ -57,6 +57,26 @@ power of two, every partial sum in any order is exact in f32 for K <= 32768
 scale, a wrong block's scale or a wrong byte select changes the fold.  No
 NaN code and no 0xFF scale appears.
 
+The further MX stages (``MX_EXT_DTYPES``, stages 4..7; a name "FA:FB" gives
+A's and Bt's formats, a single name both) take the same words, scales and
+product, and only val() is new, on the low byte w of the word:
+
+  e5m2  f = (w >> 2) & 3; code = w & 0x80 if f == 3 else
+        (w & 0x83) | ((15 + f) << 2): +-0 and +-(1 + m/4) 2**f, at most 7
+  e3m2  the same f; code = w & 0x20 if f == 3 else (w & 0x23) | ((3 + f) << 2):
+        the same values
+  e2m3  f = (w >> 3) & 3; code = w & 0x27 if f == 3 else w & 0x3F: exponent
+        field 3 folds to 0, the subnormals; at most 3.75, multiples of 1/8
+  mxfp8_e5m2 e5m2 x e5m2, mxfp6_e2m3 and mxfp6_e3m2 both operands alike,
+  mxfp8_e5m2:mxfp8 e5m2 x the e4m3 integers of mxfp8
+  fp6 in memory: 24 bytes per 32 elements, element e of the block bits
+  6e..6e+5 of that 192-bit little-endian integer; K per slab is 128 for all
+
+Bounds, in units of the product scale: products are at most 784 sixteenths
+(e5m2, e3m2) or 900 sixty-fourths (e2m3), exact up to K = 16384 (900 . 16384
+< 2**24); 448 quarters (mxfp8_e5m2:mxfp8), exact up to K = 32768 (448 . 32768
+< 2**24): ``MAX_K``.
+
 A workgroup of four waves owns a tile and wave q its quadrant q; the
 kernel walks ``t = block; t < rounds * tiles; t += blocks`` with the round
 as the slow index, and ``step_tile`` is its map from ``t % tiles`` to
@@ -73,16 +93,25 @@ The MX stages, measured on MI355X at 8192 x 8192 x 8192 in windows of 2.0
 to 2.1 s alternating with the bf16 stage (profiles/gemmcheck_mx_mi355x.json):
 1229 TFLOP/s in mxfp8 (0.895 ms per round) and 2598 TFLOP/s in mxfp4
 (0.423 ms), with bf16 at 519 TFLOP/s (2.12 ms) in the same session.
+``MX_EXT_DTYPES``, six kinds alternating in windows of 2.0 to 2.7 s
+(profiles/gemmcheck_mx6_mi355x.json): 1664 TFLOP/s in mxfp8_e5m2 (0.661 ms),
+1683 in mxfp8_e5m2:mxfp8 (0.653 ms), 1080 in mxfp6_e2m3 (1.018 ms) and 1078
+in mxfp6_e3m2 (1.020 ms), with mxfp8 at 1216 and mxfp4 at 2641 in that
+session: fp6 runs below mxfp8, for a reason not yet measured.
 
 Not covered: power, clock and temperature under load; shapes that are no
-multiple of the tile; unscaled fp8, e5m2, fp6 and mixed-width operands
-under load (mxcheck and matcheck probe those instructions in isolation);
-NaN, Inf and scale-NaN under load; address tagging finer than the four
-classes (memcheck's and vmemcheck's ground).
+multiple of the tile; unscaled fp8 and every format pair but e5m2 x e4m3
+under load (mxcheck and matcheck probe those instructions in isolation;
+e4m3 x e2m1, "mxfp8:mxfp4", was built with an LDS map of its own and gave a
+wrong product in every element on an MI355X, the way matcheck's e2m1 x e4m3
+form does: no register map is known for fp8 meeting fp4, so it is left out
+rather than compared loosely); NaN, Inf (e5m2's too) and scale-NaN under load;
+address tagging finer than the four classes (memcheck's and vmemcheck's
+ground).
 
 CLI (one JSON line; exit 0 pass, 1 mismatches, 2 could not run):
     python -m kubegpu_amd.probe.gemmcheck --device INDEX [--rounds N] [--seed S]
-                                          [--dtypes bf16,i8,mxfp8,mxfp4]
+                                          [--dtypes bf16,i8,mxfp8,mxfp4,mxfp6_e2m3,...]
 """
 
 from __future__ import annotations
@@ -96,11 +125,22 @@ from ._digest import _base, _device, _fmix32, _salt
 
 DTYPES: Tuple[str, ...] = ("bf16", "i8")  # the kernel's stage 0 and 1
 MX_DTYPES: Tuple[str, ...] = ("mxfp8", "mxfp4")  # stage 2 and 3, on request only
-_STAGES = DTYPES + MX_DTYPES
+# stages 4..7, on request only; "FA:FB" names A's and Bt's formats
+MX_EXT_DTYPES: Tuple[str, ...] = ("mxfp8_e5m2", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp8_e5m2:mxfp8")
+_STAGES = DTYPES + MX_DTYPES + MX_EXT_DTYPES
+_MX_STAGES = MX_DTYPES + MX_EXT_DTYPES
+# a one-format stage's element format; mx_formats() splits the pairs
+_ELEMENT = {"mxfp8": "e4m3", "mxfp4": "e2m1", "mxfp8_e5m2": "e5m2", "mxfp6_e2m3": "e2m3",
+            "mxfp6_e3m2": "e3m2"}
+_ELEMENT_BITS = {"e4m3": 8, "e5m2": 8, "e2m3": 6, "e3m2": 6, "e2m1": 4}
 TILE = 128
 PERIOD = 256  # rows after which the operands' content repeats
-SLAB = {"bf16": 64, "i8": 128, "mxfp8": 128, "mxfp4": 256}  # elements of K per 128-byte slab
-MAX_K = {"bf16": 32768, "i8": 131071, "mxfp8": 32768, "mxfp4": 65536}
+# elements of K per slab: 128 bytes of a row, and for MX_EXT_DTYPES 128
+# elements whatever their width
+SLAB = {"bf16": 64, "i8": 128, "mxfp8": 128, "mxfp4": 256, **{d: 128 for d in MX_EXT_DTYPES}}
+MAX_K = {"bf16": 32768, "i8": 131071, "mxfp8": 32768, "mxfp4": 65536,
+         "mxfp8_e5m2": 16384, "mxfp6_e2m3": 16384, "mxfp6_e3m2": 16384,
+         "mxfp8_e5m2:mxfp8": 32768}
 MX_BLOCK = 32  # elements of K per E8M0 scale
 _STAGE_A, _STAGE_BT = 70, 71
 _STAGE_MX_A, _STAGE_MX_BT, _STAGE_RA, _STAGE_CB, _STAGE_T = 72, 73, 74, 75, 76
@@ -176,13 +216,45 @@ def e4m3_of_int(v):
     return (np.where(mag == 0, 0, code) | np.where(np.asarray(v) < 0, 0x80, 0)).astype(np.uint8)
 
 
+def mx_formats(dtype: str) -> Tuple[str, str]:
+    """An MX stage's element formats (A's, Bt's), of e4m3, e5m2, e2m3, e3m2
+    and e2m1: "mxfp8:mxfp4" -> ("e4m3", "e2m1")."""
+    names = _check_dtype(dtype, _MX_STAGES).split(":")
+    return _ELEMENT[names[0]], _ELEMENT[names[-1]]
+
+
+def _element(fmt: str) -> str:
+    """An element format's name, given as such or as a one-format stage."""
+    fmt = _ELEMENT.get(fmt, fmt)
+    if fmt not in _ELEMENT_BITS:
+        raise ValueError(f"gemmcheck: no element format {fmt!r}")
+    return fmt
+
+
+def _val(fmt: str, w):
+    """val(): the element codes (uint8) made of words w; module docstring."""
+    import numpy as np
+
+    w = w & np.uint32(0xFF)
+    if fmt == "e4m3":
+        return e4m3_of_int(((w & 31) ^ 16).astype(np.int64) - 16)
+    if fmt == "e2m1":
+        return (w & 15).astype(np.uint8)
+    if fmt == "e2m3":
+        return np.where((w >> 3) & 3 == 3, w & 0x27, w & 0x3F).astype(np.uint8)
+    f = (w >> 2) & 3
+    sign, keep, bias = (0x80, 0x83, 15) if fmt == "e5m2" else (0x20, 0x23, 3)
+    return np.where(f == 3, w & sign, (w & keep) | ((bias + f) << 2)).astype(np.uint8)
+
+
 def mx_operand_block(seed: int, dtype: str, k: int):
     """The 256-row blocks the MX operands repeat, as uint8: (A codes [256, k],
     SA [256, k // 32], Bt codes [256, k], SB [256, k // 32]); one element
-    code per entry, e4m3 bytes or e2m1 nibbles (``mx_pack`` packs them)."""
+    code per entry, fp8 bytes, fp6 codes or e2m1 nibbles (``mx_pack`` packs
+    them)."""
     import numpy as np
 
-    _check_dtype(dtype, MX_DTYPES)
+    formats = mx_formats(dtype)
     seed, k = int(seed) & 0xFFFFFFFF, _check_k(dtype, k)
     rows = np.arange(PERIOD, dtype=np.uint32)
     idx = np.arange(k, dtype=np.uint32)
@@ -190,12 +262,8 @@ def mx_operand_block(seed: int, dtype: str, k: int):
     zero = np.zeros(1, dtype=np.uint32)
     with np.errstate(over="ignore"):
         codes = []
-        for stage in (_STAGE_MX_A, _STAGE_MX_BT):
-            w = _fmix32(_base(seed, stage, rows)[:, None] + idx[None, :])
-            if dtype == "mxfp8":
-                codes.append(e4m3_of_int(((w & np.uint32(31)) ^ np.uint32(16)).astype(np.int64) - 16))
-            else:
-                codes.append((w & np.uint32(15)).astype(np.uint8))
+        for stage, fmt in zip((_STAGE_MX_A, _STAGE_MX_BT), formats):
+            codes.append(_val(fmt, _fmix32(_base(seed, stage, rows)[:, None] + idx[None, :])))
         ra, cb = ((((_fmix32(_base(seed, stage, zero) + rows) & np.uint32(15)) ^ np.uint32(8))
                    .astype(np.int64) - 8) for stage in (_STAGE_RA, _STAGE_CB))
         t = (_fmix32(_base(seed, _STAGE_T, zero) + blocks) % np.uint32(17)).astype(np.int64) - 8
@@ -204,25 +272,34 @@ def mx_operand_block(seed: int, dtype: str, k: int):
     return codes[0], sa, codes[1], sb
 
 
-def mx_pack(dtype: str, codes):
-    """Element codes [rows, k] as the kernel reads them: e4m3 bytes as they
-    are, e2m1 nibbles two per byte with element 2b the low nibble of byte b."""
+def mx_pack(fmt: str, codes):
+    """Element codes [rows, k] of one operand as the kernel reads them.
+    ``fmt`` is its element format (or a one-format stage): fp8 bytes as they
+    are; e2m1 nibbles two per byte with element 2b the low nibble of byte b;
+    fp6 codes 24 bytes per 32 elements, element e of a block bits 6e..6e+5
+    of that 192-bit little-endian integer."""
     import numpy as np
 
     codes = np.ascontiguousarray(codes, dtype=np.uint8)
-    if _check_dtype(dtype, MX_DTYPES) == "mxfp8":
+    bits = _ELEMENT_BITS[_element(fmt)]
+    if bits == 8:
         return codes
-    return codes[:, 0::2] | (codes[:, 1::2] << 4)
+    if bits == 4:
+        return codes[:, 0::2] | (codes[:, 1::2] << 4)
+    each = np.unpackbits(codes[:, :, None], axis=2, bitorder="little")[:, :, :6]
+    return np.packbits(each.reshape(codes.shape[0], -1), axis=1, bitorder="little")
 
 
-def mx_dequantise(dtype: str, codes, scales):
-    """The float64 values codes [rows, k] and E8M0 scales [rows, k // 32]
-    stand for (exact)."""
+def mx_dequantise(fmt: str, codes, scales):
+    """The float64 values codes [rows, k] of element format ``fmt`` (or a
+    one-format stage) and E8M0 scales [rows, k // 32] stand for (exact)."""
     import numpy as np
 
-    from .mxcheck import E2M1, E4M3
+    from .matcheck import E2M3, E3M2
+    from .mxcheck import E2M1, E4M3, E5M2
 
-    table = np.array(E4M3 if _check_dtype(dtype, MX_DTYPES) == "mxfp8" else E2M1)
+    table = np.array({"e4m3": E4M3, "e5m2": E5M2, "e2m3": E2M3, "e3m2": E3M2,
+                      "e2m1": E2M1}[_element(fmt)])
     exp = np.repeat(np.asarray(scales).astype(np.int64), MX_BLOCK, axis=1) - 127
     return np.ldexp(table[np.asarray(codes)], exp)
 
@@ -237,8 +314,9 @@ def mx_operands(seed: int, dtype: str, m: int, n: int, k: int, device=None):
         raise ValueError(f"gemmcheck: M and N must be multiples of {TILE}, got {m} and {n}")
     device = _device(device)
     a, sa, bt, sb = mx_operand_block(seed, dtype, k)
+    fa, fb = mx_formats(dtype)
     out = []
-    for block, rows in ((mx_pack(dtype, a), m), (sa, m), (mx_pack(dtype, bt), n), (sb, n)):
+    for block, rows in ((mx_pack(fa, a), m), (sa, m), (mx_pack(fb, bt), n), (sb, n)):
         t = torch.from_numpy(block).to(device)
         out.append(t.repeat(-(-rows // PERIOD), 1)[:rows].contiguous())
     return tuple(out)
@@ -282,9 +360,10 @@ def reference_expected(seed: int, dtype: str, k: int):
     GPU kernel is tested against."""
     import numpy as np
 
-    if dtype in MX_DTYPES:
+    if dtype in _MX_STAGES:
         a, sa, bt, sb = mx_operand_block(seed, dtype, k)
-        a, bt = mx_dequantise(dtype, a, sa), mx_dequantise(dtype, bt, sb)
+        fa, fb = mx_formats(dtype)
+        a, bt = mx_dequantise(fa, a, sa), mx_dequantise(fb, bt, sb)
     else:
         a, bt = operand_block(seed, dtype, k)
     c = a.astype(np.float64) @ bt.astype(np.float64).T  # exact: see the module docstring
@@ -358,10 +437,11 @@ def gemmcheck(
     """Run ``rounds`` GEMMs of [m, k] by [n, k] per dtype in one launch each
     on ``blocks`` workgroups of four waves (0 = two per CU, or one per tile
     step if that is fewer) and compare every wave's fold with
-    ``reference_expected``.  ``dtypes`` may name any of ``DTYPES`` and
-    ``MX_DTYPES``; the default is ``DTYPES``.
+    ``reference_expected``.  ``dtypes`` may name any of ``DTYPES``,
+    ``MX_DTYPES`` and ``MX_EXT_DTYPES``; the default is ``DTYPES``.
 
-    The operands are taken from free VRAM: 2 (m + n) k bytes at most; where
+    The operands are taken from free VRAM: 2 (m + n) k bytes at most (bf16;
+    every MX stage is at most a byte per element and one per 32 of scale); where
     they do not fit the probe raises, which says nothing about the hardware.
 
     ``_inject=(dtype, wave of the grid, round, xor_mask)`` flips bits of
@@ -389,7 +469,7 @@ def gemmcheck(
             inject = None
             if _inject is not None and _inject[0] == dtype:
                 inject = (int(_inject[1]), int(_inject[2]), stage, int(_inject[3]))
-            if dtype in MX_DTYPES:
+            if dtype in _MX_STAGES:
                 ops = mx_operands(seed, dtype, m, n, k, device)
                 raw = ext.gemmcheck_mx_run(*ops, dtype, expected, rounds, blocks,
                                            int(max_records), inject)
@@ -433,7 +513,12 @@ def gemm_mx_nt(a, a_scale, bt, bt_scale, format: str, blocks: int = 0):
     ``format`` "mxfp8": ``a [M, K]``, ``bt [N, K]`` hold e4m3 codes (uint8 or
     float8_e4m3fn), K a multiple of 128, at most 32768.  "mxfp4": ``a [M, K / 2]``,
     ``bt [N, K / 2]`` uint8 hold two e2m1 codes per byte, the low nibble
-    first, K a multiple of 256, at most 65536.  The scales are uint8 E8M0,
+    first, K a multiple of 256, at most 65536.  "mxfp8_e5m2": e5m2 codes
+    (uint8 or float8_e5m2) ``[M, K]``, ``[N, K]``; "mxfp6_e2m3" and
+    "mxfp6_e3m2": ``a [M, 3 K / 4]``, ``bt [N, 3 K / 4]`` uint8, 24 bytes per
+    32 elements, element e of a block bits 6e..6e+5 of that little-endian
+    integer; "mxfp8_e5m2:mxfp8": e5m2 ``a`` and e4m3 ``bt``, both ``[.., K]``;
+    for these four K is a multiple of 128 (MAX_K at most).  The scales are uint8 E8M0,
     ``[M, K / 32]`` and ``[N, K / 32]``; M and N multiples of 128.  Exact
     whenever every partial sum is representable in float32.  ``blocks``
     workgroups walk the tiles (0 = two per CU)."""
